@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched 7-DoF RNEA + gradient evaluations per second (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch B]
+    python bench.py [--gpus N --steps K --warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,17 +11,24 @@ calls of the reference's ``rnea_grad`` (``/root/reference/RBDReference.py:1345-1
 BASELINE.json configs[3] ("7-DoF iiwa rnea_grad batch=1M sharded across 8xMI355X"): a GLOBAL batch of
 ``--batch`` (1 048 576) rows, rank r evaluating rows ``shard_bounds(B, world, r)`` -- strong scaling,
 the configuration as written, no data-path collective (rows are independent).  With
-``--scaling weak`` every rank evaluates its own ``--batch`` rows instead.  Under torchrun the other mode
-is measured in the same run and reported as a second object (``"weak"`` / ``"strong"``); at N = 1 the
-two coincide.  Every step uses the next of ``--rotate`` (default 4) input/output buffer sets, so
-that more input bytes are in flight (4 x 88 MB) than the 256 MB Infinity Cache holds.  configs[1]
-(B = 4096) is reported beside it under "extra" -- at that size a launch is latency-bound and says
-nothing about the roofline.
+``--scaling weak`` every rank evaluates its own ``--batch`` rows instead.  Every step uses the next of
+``--rotate`` (default 4) input/output buffer sets, so that more input bytes are in flight (4 x 88 MB)
+than the 256 MB Infinity Cache holds.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
-``roofline`` (algorithmic HBM bytes per launch / measured kernel time vs the 8 TB/s peak; the
-kernel is FP32-VALU-bound, so the VALU fraction is reported too) and ``cpu_baseline`` (the CPU
-oracle timed on this host's cores on a bounded sample of the same workload).
+A plain run sets up, warms up, times exactly ``--steps`` steps and prints ONE JSON line on rank 0
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = wall milliseconds of
+one timed step) with ``roofline`` (algorithmic HBM bytes per launch / the same steps' HIP-event kernel
+time vs the 8 TB/s peak; the kernel is FP32-VALU-bound, so the VALU fraction is reported too).
+``--dump-outputs DIR`` writes what the last timed step computed, ``c`` and ``dc_du`` (fp32) of a fixed,
+seeded sample of the global batch's rows (all rows when they fit in 64 MB), as ``DIR/c.npy`` and
+``DIR/dc_du.npy``; the inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds everything that takes runs of its own: a parity spot-check of the timed outputs against
+the fp64 oracle, under torchrun the other scaling mode (``"weak"`` / ``"strong"``; at N = 1 the two
+coincide), ``extra`` (the other BASELINE configurations, precisions and kernels, e.g. configs[1] at
+B = 4096, where a launch is latency-bound and says nothing about the roofline) and ``cpu_baseline``
+(the CPU oracle timed on this host's cores on a bounded sample of the same workload);
+``--no-extra`` / ``--no-cpu-baseline`` leave out those two.
 """
 import argparse
 import json
@@ -54,8 +61,12 @@ def parse():
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="time the K steps as ONE replay of a HIP graph of K launches (auto: strong scaling on more than one GPU, "
                          "where a rank's shard is small enough for the launch path to show)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write c and dc_du of the last timed step (a fixed, seeded row sample, at most 64 MB) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity spot-check, the other scaling mode, the extra configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) leave out the extra configurations")
     return ap.parse_args()
 
 
@@ -71,7 +82,7 @@ def make_inputs(B, n, seed, device, dtype=torch.float32):
 
 class GradStep:
     """Pre-allocated buffers + a direct C-ABI launch on torch's current stream.  `sets` input/output
-    buffer sets are used round-robin (each call takes the next one)."""
+    buffer sets are used round-robin (each call takes the next one; `last` is the set the latest launch wrote)."""
 
     def __init__(self, rbd, inputs):
         self.rbd = rbd
@@ -86,6 +97,7 @@ class GradStep:
         self.args = [(a.data_ptr(), b.data_ptr(), c_.data_ptr(), -9.81, 0, B, o[0].data_ptr(), o[1].data_ptr(), self.stream)
                      for (a, b, c_), o in zip(inputs, self.outs)]
         self.k = 0
+        self.last = None
 
     @property
     def dc(self):
@@ -93,6 +105,7 @@ class GradStep:
 
     def __call__(self):
         a = self.args[self.k]
+        self.last = self.k
         self.k = (self.k + 1) % len(self.args)
         rc = self.fn(*a)
         if rc != 0:
@@ -101,6 +114,7 @@ class GradStep:
     def on_stream(self, st):
         """The next launch on stream `st` (a raw hipStream_t) instead of the stream this object was built on."""
         a = self.args[self.k]
+        self.last = self.k
         self.k = (self.k + 1) % len(self.args)
         rc = self.fn(*a[:-1], st)
         if rc != 0:
@@ -121,11 +135,13 @@ class GraphSteps:
             step.on_stream(side.cuda_stream)            # everything the launch path sets up lazily happens outside the capture
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize()
+        step.k = 0                                      # the replay writes sets 0, 1, ... like the eager timed steps (timed_steps)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             st = torch.cuda.current_stream(dev).cuda_stream
             for _ in range(K):
                 step.on_stream(st)
+        self.last = step.last                           # the buffer set the replay's last launch writes
 
     def __call__(self):
         self.graph.replay()
@@ -225,6 +241,40 @@ def sources_digest():
     return h.hexdigest()[:16]
 
 
+DUMP_ROWS = 1 << 16            # --dump-outputs: rows sampled when the whole batch exceeds DUMP_BYTES_MAX
+DUMP_BYTES_MAX = 60 * 10**6   # (the .npy headers stay within 64 MB too)
+DUMP_SEED = 2024
+
+
+def dump_outputs(dirpath, outs, rows_global, lo, dist, rank):
+    """--dump-outputs: `outs` = (c, dc_du) of the last timed step, this rank's rows [lo, lo + B) of the global batch.
+    Writes DIR/c.npy [S, n] and DIR/dc_du.npy [S, n, 2n] (fp32, as the kernel wrote them) for S rows of the global
+    batch: all of them when they fit in DUMP_BYTES_MAX, else DUMP_ROWS rows drawn once with DUMP_SEED, in row order
+    (gathered on rank 0).  Returns what was written (rank 0) or None."""
+    c, dc = outs
+    B = c.shape[0]
+    row_bytes = (c[0].numel() + dc[0].numel()) * c.element_size()
+    if rows_global * row_bytes <= DUMP_BYTES_MAX:
+        rows, sample = np.arange(rows_global), "all rows"
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(rows_global, size=DUMP_ROWS, replace=False))
+        sample = f"{DUMP_ROWS} rows of {rows_global} (numpy default_rng({DUMP_SEED}).choice, sorted)"
+    mine = torch.from_numpy(rows[(rows >= lo) & (rows < lo + B)] - lo).to(c.device)
+    part = (c.index_select(0, mine).cpu().numpy(), dc.index_select(0, mine).cpu().numpy())
+    if dist is not None:
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)           # ranks hold ascending row ranges
+    else:
+        parts = [part]
+    if rank != 0:
+        return None
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {"c": np.concatenate([p[0] for p in parts]), "dc_du": np.concatenate([p[1] for p in parts])}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {"dir": dirpath, "rows": sample, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 def pick_graph(step, steps, dist, dev):
     """--graph auto, strong scaling on several GPUs: an UNTIMED calibration decides how the K timed launches are issued.
     The same K launches, eager and as one replay of a HIP graph, are timed once each (after a replay for the graph's
@@ -266,12 +316,16 @@ def pick_graph(step, steps, dist, dev):
 
 def timed_steps(step, steps, warmup, dist, dev, graph=False, prebuilt=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides.
-    Returns (wall seconds, HIP-event ms per step on the launch stream): this rank's.
+    Returns (wall seconds, HIP-event ms per step on the launch stream, the buffer set the last timed step wrote): the
+    times are the max over ranks.
     graph: the K steps are captured (untimed) into one HIP graph and the timed region is its replay -- the same K launches."""
     run = None
     if graph:
         gs = prebuilt if prebuilt is not None else GraphSteps(step, steps, dev)
         run = gs
+    # the clock ramp ran for a time, not a count: the rotation is restarted so that the timed steps use buffer sets 0, 1, ...
+    # (as the graph's replay does) in every run, right after warm-up steps on the sets before them (--dump-outputs)
+    step.k = (-warmup) % len(step.args)
     for _ in range(warmup):
         step()
     if run is not None:
@@ -296,6 +350,7 @@ def timed_steps(step, steps, warmup, dist, dev, graph=False, prebuilt=None):
     ev1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0          # this rank's K steps, device-synchronised; MAX over ranks below
+    last = run.last if run is not None else step.last
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -304,7 +359,7 @@ def timed_steps(step, steps, warmup, dist, dev, graph=False, prebuilt=None):
         t = torch.tensor([wall, kern_ms], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, kern_ms = t[0].item(), t[1].item()
-    return wall, kern_ms
+    return wall, kern_ms, last
 
 
 def main():
@@ -370,17 +425,21 @@ def main():
     if args.graph == "auto" and (world > 1 or os.environ.get("RBD_BENCH_CALIBRATE")) and args.scaling == "strong":   # (env: rehearse the calibration on one GPU)
         use_graph, prebuilt, graph_cal = pick_graph(step, args.steps, dist, dev)
         ramp()                               # (the capture and instantiation left the GPU idle: back to the working clock)
-    wall, kern_ms = timed_steps(step, args.steps, args.warmup, dist, dev, graph=use_graph, prebuilt=prebuilt)
+    wall, kern_ms, last = timed_steps(step, args.steps, args.warmup, dist, dev, graph=use_graph, prebuilt=prebuilt)
+    dumped = None
+    if args.dump_outputs:
+        lo = shard_bounds(B, world, rank)[0] if args.scaling == "strong" else rank * B
+        dumped = dump_outputs(args.dump_outputs, step.outs[last], B if args.scaling == "strong" else world * B, lo, dist, rank)
 
     other = None
-    if world > 1:                            # the other scaling mode, same run, reported beside the headline
+    if world > 1 and args.full:              # the other scaling mode, same run, reported beside the headline
         omode = "weak" if args.scaling == "strong" else "strong"
         ostep = make_step(omode)
         rbd._lib.set_option(RBD_OPT_SELECT_BATCH, B if omode == "strong" else 0)
         og, opre = args.graph == "on", None
         if args.graph == "auto" and omode == "strong":
             og, opre, _ = pick_graph(ostep, args.steps, dist, dev)
-        ow, ok = timed_steps(ostep, args.steps, args.warmup, dist, dev, graph=og, prebuilt=opre)
+        ow, ok, _ = timed_steps(ostep, args.steps, args.warmup, dist, dev, graph=og, prebuilt=opre)
         rbd._lib.set_option(RBD_OPT_SELECT_BATCH, 0)
         orows = B if omode == "strong" else world * B
         other = {"scaling": omode, "value": orows * args.steps / ow, "unit": "evals/s", "ms_per_step": ow / args.steps * 1e3,
@@ -390,7 +449,7 @@ def main():
     rbd._lib.set_option(RBD_OPT_SELECT_BATCH, 0)
     # parity spot-check of what was just timed (first 256 rows of buffer set 0 vs the fp64 oracle), rank 0
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import rbd_oracle as orc
         om = orc.model_from_robot(robot)
         k = min(256, rows_rank)
@@ -458,12 +517,15 @@ def main():
                                  "sources) / this run's launch time / 157.3 TFLOP/s; valu_issue_frac = all VALU "
                                  "wave-instructions x 2 cycles per SIMD / launch cycles (what the vector pipe is busy); "
                                  "`bound` names the larger of frac and valu_frac_of_peak"},
-            "parity_max_rel_err_first_256_rows": parity,
         }
+        if parity is not None:
+            out["parity_max_rel_err_first_256_rows"] = parity
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if other is not None:
             out[other["scaling"]] = other
         q, qd, qdd = step.inputs[0]
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             extra = {}
             # BASELINE configs[1]: B = 4096, rnea + rnea_grad back to back
             q4, qd4, qdd4 = make_inputs(4096, N_DOF, 1, dev)
@@ -726,7 +788,7 @@ def main():
             except Exception as e:
                 extra["traffic_error"] = repr(e)
             out["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(robot, 3)
         print(json.dumps(out))
     if dist is not None:

@@ -5,7 +5,7 @@
 set -u
 OUT=gpurun_out/${1:-prof}
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 300 python3 bench.py --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err; echo bench_rc=$?
+timeout -k 10 300 python3 bench.py --steps 50 --warmup 10 --full > $OUT/bench.json 2> $OUT/bench.err; echo bench_rc=$?
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -- python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extra > $OUT/bench_prof.json 2> $OUT/bench_prof.err; echo benchprof_rc=$?
 REPS=20 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/configs_stats -- python3 tools/run_configs.py > $OUT/configs.log 2>&1; echo configs_rc=$?
 for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_INSTS_SMEM" "SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32" "FETCH_SIZE" "WRITE_SIZE"; do
