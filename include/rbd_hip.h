@@ -249,6 +249,23 @@ int rbd_forward_dynamics_grad_f64(const double* q, const double* qd, const doubl
                                   int64_t B, double* qdd, double* dqdd_du, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* RBDReference.end_effector_pose / end_effector_pose_gradient        (RBDReference.py:220-274, :286-386)
+ * Fixed-base robots; a floating-base library returns RBD_ERR_UNSUPPORTED.  ONE launch computes pose, gradient or both.
+ *   q         : [B, n] device
+ *   site_body : int32 [n_sites], HOST -- body whose frame carries site s (0 <= id < n)
+ *   site_T    : double [n_sites][12], HOST -- constant body -> site transform [R | t], row-major 3 x 4 (identity for the
+ *               joint's link frame, the fixed frame's pose for a fixed joint)
+ *   offset    : double [4], HOST -- ee_offsets[0] = (x, y, z, w) of the reference, shared by every site
+ *   n_sites   : 1 .. RBD_EE_MAX_SITES, passed to the kernel by value
+ *   pose      : [B, n_sites, 6]    xyz of R_s o + w t_s, then roll / pitch / yaw as the reference extracts them (:245-258)
+ *   dpose     : [B, n_sites, 6, n] d pose / d q; zero columns for joints off the site's chain (:357-359, :378-380)
+ *   Either output may be NULL (not both).  Arguments are checked before anything touches the GPU; B == 0 is a no-op. */
+#define RBD_EE_MAX_SITES 16
+int rbd_ee_pose_f32(const float* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset,
+                    int n_sites, float* pose, float* dpose, void* stream);
+int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset,
+                    int n_sites, double* pose, double* dpose, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

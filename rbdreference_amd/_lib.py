@@ -39,7 +39,9 @@ EXPORTED_SYMBOLS = [
     "rbd_rnea_grad_bpass_dqd_f32", "rbd_rnea_grad_bpass_dqd_f64",
     "rbd_aba_f32", "rbd_aba_f64",
     "rbd_minv_bpass_f32", "rbd_minv_bpass_f64", "rbd_minv_fpass_f32", "rbd_minv_fpass_f64",
+    "rbd_ee_pose_f32", "rbd_ee_pose_f64",
 ]
+RBD_EE_MAX_SITES = 16
 
 
 class RbdModelInfo(Structure):
@@ -111,6 +113,10 @@ def _declare(lib):
             f = getattr(lib, f"{nm}_{sfx}")
             f.restype = c_int
             f.argtypes = at
+    for sfx in ("f32", "f64"):
+        f = getattr(lib, f"rbd_ee_pose_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.rbd_minv_workspace_bytes.restype = c_size_t
     lib.rbd_minv_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_fd_workspace_bytes.restype = c_size_t

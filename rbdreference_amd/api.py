@@ -779,3 +779,115 @@ class RBDReference:
         n = self.nv
         d = self._ret(d, unb, is_np)
         return d[..., :n], d[..., n:]
+
+    # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
+    def _ee_plan(self, ee_joint_names, ee_offsets):
+        """Site table of a selection, resolved once and cached: ``(chunks of (site_body int32 [k], site_T float64 [k, 12]),
+        offset float64 [4], n_sites)`` in the reference's order -- every movable joint as given, then every fixed joint
+        (``select_end_effector_joints``, :190-210; :263-273)."""
+        if self.model.floating:
+            raise NotImplementedError("end-effector kinematics: fixed-base robots only (the reference's end_effector_pose "
+                                      "has no floating-base support, RBDReference.py:217)")
+        o = np.asarray(ee_offsets[0], dtype=np.float64).reshape(-1)
+        if o.size != 4:
+            raise ValueError(f"ee_offsets[0] must hold 4 numbers (x, y, z, 1), got {o.size}")
+        names = None if ee_joint_names is None else (ee_joint_names,) if isinstance(ee_joint_names, str) else tuple(ee_joint_names)
+        key = (names, o.tobytes())
+        cache = self.__dict__.setdefault("_ee_plans", {})
+        plan = cache.get(key)
+        if plan is not None:
+            return plan
+        r = self.robot
+        frame = getattr(r, "link_frame_in_body", None)
+
+        def link_in_body(i):
+            T = np.eye(4)
+            if frame is not None:
+                T[:3, :3] = frame(i)
+            return T
+        if names is None:
+            sites = [(int(j), link_in_body(int(j))) for j in r.get_leaf_nodes()]
+        else:
+            mov, fix = [], []
+            for nm in names:
+                j = r.get_joint_by_name(nm)
+                if j is not None:
+                    mov.append((int(j.get_id()), link_in_body(int(j.get_id()))))
+                    continue
+                fj = r.get_fixed_joint_by_name(nm)
+                if fj is None:
+                    raise ValueError("Could not find joint or fixed joint named: " + str(nm))
+                body = int(r.get_joint_by_name(fj.parent_name).get_id())
+                fix.append((body, link_in_body(body) @ np.asarray(fj.get_transformation_matrix_hom(), dtype=np.float64)))
+            sites = mov + fix
+        from ._lib import RBD_EE_MAX_SITES
+        chunks = []
+        for k in range(0, len(sites), RBD_EE_MAX_SITES):
+            part = sites[k:k + RBD_EE_MAX_SITES]
+            chunks.append((np.ascontiguousarray([b for b, _ in part], dtype=np.int32),
+                           np.ascontiguousarray([T[:3, :].reshape(12) for _, T in part], dtype=np.float64)))
+        plan = (chunks, np.ascontiguousarray(o), len(sites))
+        if len(cache) >= 64:
+            cache.pop(next(iter(cache)))
+        cache[key] = plan
+        return plan
+
+    def _ee(self, q, ee_joint_names, ee_offsets, want_pose, want_grad):
+        chunks, off, ns = self._ee_plan(ee_joint_names, ee_offsets)
+        (q,), unb, is_np, dev, dt = self._prep(q)
+        B, n = q.shape[0], self.n
+        sfx = "f32" if dt == torch.float32 else "f64"
+        with torch.cuda.device(dev):
+            pose = torch.empty((B, ns, 6), device=dev, dtype=dt) if want_pose else None
+            dpose = torch.empty((B, ns, 6, n), device=dev, dtype=dt) if want_grad else None
+            st = torch.cuda.current_stream(dev).cuda_stream
+            fn = self._lib.fn("rbd_ee_pose", sfx)
+            if len(chunks) == 1:
+                body, T = chunks[0]
+                self._lib.check(fn(self._ptr(q), B, body.ctypes.data, T.ctypes.data, off.ctypes.data, len(body),
+                                   self._ptr(pose), self._ptr(dpose), st))
+            else:                                 # > RBD_EE_MAX_SITES sites: one launch per chunk into its own buffers
+                ps, ds = [], []
+                for body, T in chunks:
+                    k = len(body)
+                    p = torch.empty((B, k, 6), device=dev, dtype=dt) if want_pose else None
+                    d = torch.empty((B, k, 6, n), device=dev, dtype=dt) if want_grad else None
+                    self._lib.check(fn(self._ptr(q), B, body.ctypes.data, T.ctypes.data, off.ctypes.data, k,
+                                       self._ptr(p), self._ptr(d), st))
+                    ps.append(p); ds.append(d)
+                if want_pose:
+                    torch.cat(ps, dim=1, out=pose)
+                if want_grad:
+                    torch.cat(ds, dim=1, out=dpose)
+        return pose, dpose, unb, is_np
+
+    @staticmethod
+    def _ee_ret(x, unb, is_np, col):
+        """Batched: the [B, n_ee, ...] array / tensor.  One configuration: the reference's list of (6, 1) / (6, n)
+        per end effector (np.matrix for numpy inputs, as the reference's np.vstack / np.hstack of matrices gives)."""
+        if not unb:
+            return x.cpu().numpy() if is_np else x
+        x = x[0]
+        if is_np:
+            x = x.cpu().numpy()
+            return [np.matrix(e.reshape(6, 1) if col else e) for e in x]
+        return [e.reshape(6, 1) if col else e for e in x]
+
+    def end_effector_pose(self, q, ee_joint_names=None, ee_offsets=[np.matrix([[0, 0, 0, 1]])]):  # noqa: B006 (reference signature)
+        """RBDReference.end_effector_pose (``RBDReference.py:220-274``): per end effector ``[x, y, z, roll, pitch, yaw]``.
+        ``ee_joint_names=None``: every leaf joint; else movable joints in the given order, then fixed joints.  Only
+        ``ee_offsets[0]`` is used, for every end effector, as in the reference (:245).  ``q [n]`` -> list of (6, 1);
+        ``q [B, n]`` -> ``[B, n_ee, 6]``."""
+        pose, _, unb, is_np = self._ee(q, ee_joint_names, ee_offsets, True, False)
+        return self._ee_ret(pose, unb, is_np, True)
+
+    def end_effector_pose_gradient(self, q, ee_joint_names=None, ee_offsets=[np.matrix([[0, 0, 0, 1]])]):  # noqa: B006
+        """RBDReference.end_effector_pose_gradient (``RBDReference.py:286-386``): d pose / d q per end effector, zero
+        columns for joints off its chain.  ``q [n]`` -> list of (6, n); ``q [B, n]`` -> ``[B, n_ee, 6, n]``."""
+        _, dpose, unb, is_np = self._ee(q, ee_joint_names, ee_offsets, False, True)
+        return self._ee_ret(dpose, unb, is_np, False)
+
+    def end_effector_pose_and_gradient(self, q, ee_joint_names=None, ee_offsets=[np.matrix([[0, 0, 0, 1]])]):  # noqa: B006
+        """``(end_effector_pose(...), end_effector_pose_gradient(...))`` from ONE launch (like ``rnea_and_grad``)."""
+        pose, dpose, unb, is_np = self._ee(q, ee_joint_names, ee_offsets, True, True)
+        return self._ee_ret(pose, unb, is_np, True), self._ee_ret(dpose, unb, is_np, False)

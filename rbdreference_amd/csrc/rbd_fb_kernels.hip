@@ -428,6 +428,10 @@ __attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f64(void);
     RbdStreamDevice sd_(stream); return minv_fpass_fb_launch<T>(q, B, Minv, F, U, Dinv, stream);                                                         \
   }                                                                                                                         \
   int rbd_crba_##SFX(const T*, int64_t, T*, void*) { return unsupported("rbd_crba"); }                                      \
+  int rbd_ee_pose_##SFX(const T*, int64_t, const int32_t*, const double*, const double*, int, T*, T*, void*) {             \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_ee_pose: fixed-base robots only (the reference's end_effector_pose has no "      \
+                "floating-base support, RBDReference.py:217)");                                                            \
+  }                                                                                                                         \
   int rbd_aba_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) { return unsupported("rbd_aba"); }                 \
   int rbd_forward_dynamics_grad_##SFX(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, void* ws, \
                                       size_t wsb, void* stream) {                                                           \

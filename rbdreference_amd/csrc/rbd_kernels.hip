@@ -47,6 +47,8 @@
 #define RBD_TU_FD_F64 1
 #define RBD_TU_PASS_F32 1
 #define RBD_TU_PASS_F64 1
+#define RBD_TU_EE_F32 1
+#define RBD_TU_EE_F64 1
 #endif
 
 // Which kernel families this unit needs (everything it does not need is dropped by the preprocessor,
@@ -66,6 +68,9 @@
 #endif
 #if defined(RBD_TU_PASS_F32) || defined(RBD_TU_PASS_F64)
 #define RBD_NEED_PASS 1
+#endif
+#if defined(RBD_TU_EE_F32) || defined(RBD_TU_EE_F64)
+#define RBD_NEED_EE 1
 #endif
 #include "rbd_spatial.h"
 
@@ -2061,6 +2066,9 @@ __global__ __launch_bounds__(64 * MINV_COLS_W, MINV_COLS_MIN_WAVES) void minv_co
 #ifdef RBD_NEED_PASS
 #include "rbd_passes.h"
 #endif
+#ifdef RBD_NEED_EE
+#include "rbd_ee.h"
+#endif
 namespace rbdk {
 #ifdef RBD_NO_MINV_LANE
 template <class T>
@@ -2920,6 +2928,61 @@ int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd,
 }
 #endif  // RBD_NEED_FD
 
+#ifdef RBD_NEED_EE
+// rbd_ee_pose: site table (host arrays) -> EeSites kernel argument; one launch for pose, gradient or both
+template <class T>
+int ee_launch(const T* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
+              T* pose, T* dpose, void* stream) {
+  using namespace rbdk;
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_ee_pose: fixed-base robots only");
+  if (n_sites < 1 || n_sites > RBD_EE_MAX_SITES) return fail(RBD_ERR_ARG, "rbd_ee_pose: n_sites must be in [1, RBD_EE_MAX_SITES]");
+  if (!site_body || !site_T || !offset) return fail(RBD_ERR_ARG, "rbd_ee_pose: site_body, site_T and offset must be non-null");
+  EeSites<T> st;
+  std::memset(&st, 0, sizeof(st));
+  st.n_sites = n_sites;
+  const double w = offset[3];
+  st.w = (T)w;
+  for (int s = 0; s < n_sites; ++s) {
+    if (site_body[s] < 0 || site_body[s] >= rbdm::N) return fail(RBD_ERR_ARG, "rbd_ee_pose: site body id out of range");
+    st.body[s] = site_body[s];
+    const double* M = site_T + 12 * s;              // [R | t] row-major 3 x 4
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) st.M[s][3 * r + c] = (T)M[4 * r + c];
+      st.pl[s][r] = (T)(M[4 * r] * offset[0] + M[4 * r + 1] * offset[1] + M[4 * r + 2] * offset[2] + w * M[4 * r + 3]);
+    }
+  }
+  if (B < 0) return fail(RBD_ERR_ARG, "rbd_ee_pose: B < 0");
+  if (B == 0) return 0;                             // (empty outputs may come as null pointers)
+  if (!q) return fail(RBD_ERR_ARG, "rbd_ee_pose: q must be non-null");
+  if (!pose && !dpose) return fail(RBD_ERR_ARG, "rbd_ee_pose: pose and dpose are both null");
+  if (((reinterpret_cast<uintptr_t>(pose) | reinterpret_cast<uintptr_t>(dpose)) & 15u) != 0)
+    return fail(RBD_ERR_ARG, "rbd_ee_pose: output buffers must be 16-byte aligned");
+  const int64_t blocks = (B + 63) / 64;
+  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_ee_pose: B too large");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t lds = ee_lds_bytes<T>(n_sites, pose != nullptr, dpose != nullptr);
+  if (lds > 160 * 1024)             // (a robot near RBD_MAX_BODIES in fp64: its [64][6n] gradient tile alone)
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_ee_pose: the q / pose / gradient tiles exceed the 160 KB of LDS of a CU for this "
+                                     "robot and precision; pass fewer sites per call");
+  int rc;
+  if (pose && dpose) {
+    auto k = ee_pose_kernel<T, true, true>;
+    if ((rc = ensure_lds(k, lds)) != 0) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
+  } else if (pose) {
+    auto k = ee_pose_kernel<T, true, false>;
+    if ((rc = ensure_lds(k, lds)) != 0) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
+  } else {
+    auto k = ee_pose_kernel<T, false, true>;
+    if ((rc = ensure_lds(k, lds)) != 0) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
+  }
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "rbd_ee_pose launch");
+}
+#endif  // RBD_NEED_EE
+
 #if defined(RBD_TU_PASS_F32) || defined(RBD_TU_PASS_F64)
 // ---- per-pass entry points (rbd_passes.h) ------------------------------------------------------------
 int pass_blocks(int64_t B, const char* who, unsigned* blocks) {
@@ -3246,6 +3309,18 @@ int rbd_minv_fpass_f64(const double* q, int64_t B, double* Minv, double* F, cons
   RbdStreamDevice sd_(stream); return minv_fpass_launch<double>(q, B, Minv, F, U, Dinv, stream);
 }
 #endif
+#ifdef RBD_TU_EE_F32
+int rbd_ee_pose_f32(const float* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
+                    float* pose, float* dpose, void* stream) {
+  RbdStreamDevice sd_(stream); return ee_launch<float>(q, B, site_body, site_T, offset, n_sites, pose, dpose, stream);
+}
+#endif
+#ifdef RBD_TU_EE_F64
+int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
+                    double* pose, double* dpose, void* stream) {
+  RbdStreamDevice sd_(stream); return ee_launch<double>(q, B, site_body, site_T, offset, n_sites, pose, dpose, stream);
+}
+#endif
 
 // ---- stubs (-DRBD_TU_STUBS with -DRBD_STUB_<unit> per missing unit): a FAMILY library holds COMMON, the units of one
 // family and these, so that it links and loads like a full library; an entry point of another family says so ------
@@ -3280,6 +3355,14 @@ int rbd_minv_fpass_f64(const double* q, int64_t B, double* Minv, double* F, cons
   int rbd_rnea_grad_bpass_dqd_##SFX(const T*, T*, int, int64_t, T*, void*) RBD_STUB_BODY("rbd_rnea_grad_bpass_dqd")              \
   int rbd_minv_bpass_##SFX(const T*, int64_t, T*, T*, T*, T*, void*) RBD_STUB_BODY("rbd_minv_bpass")                             \
   int rbd_minv_fpass_##SFX(const T*, int64_t, T*, T*, const T*, const T*, void*) RBD_STUB_BODY("rbd_minv_fpass")
+#define RBD_STUBS_EE(SFX, T)                                                                                                     \
+  int rbd_ee_pose_##SFX(const T*, int64_t, const int32_t*, const double*, const double*, int, T*, T*, void*) RBD_STUB_BODY("rbd_ee_pose")
+#ifdef RBD_STUB_EE_F32
+RBD_STUBS_EE(f32, float)
+#endif
+#ifdef RBD_STUB_EE_F64
+RBD_STUBS_EE(f64, double)
+#endif
 #ifdef RBD_STUB_RNEA_F32
 RBD_STUBS_RNEA(f32, float)
 #endif

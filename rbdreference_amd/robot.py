@@ -33,7 +33,7 @@ from typing import Callable, Dict, List, Sequence
 
 import numpy as np
 
-__all__ = ["Link", "Robot", "FloatingBaseRobot", "floating_base_X", "iiwa_like", "quadruped_like",
+__all__ = ["Link", "Robot", "FixedFrame", "FloatingBaseRobot", "floating_base_X", "iiwa_like", "quadruped_like",
            "atlas_like", "random_tree", "floating_quadruped_like", "BUILTIN_ROBOTS", "builtin_robot"]
 
 
@@ -103,6 +103,40 @@ class Link:
     jtype: str = "revolute"           # or "prismatic"
     rot: object = None                # optional 3x3 E (child-frame coords of parent-frame vectors);
                                       # overrides rpy (used by the URDF loader for arbitrary frames)
+    frame: object = None              # optional 3x3 rotation: orientation of the body frame in the body's
+                                      # (URDF) link frame; None = the link frame IS the body frame.  Read
+                                      # only by the kinematics getters (get_Xmat_hom_Func_by_id), never packed
+
+
+class _Joint:
+    """What the reference's joint look-ups return (``RBDReference.py:190-210, :263-273``)."""
+
+    def __init__(self, jid: int, name: str):
+        self._id = int(jid)
+        self.name = name
+
+    def get_id(self) -> int:
+        return self._id
+
+    def __repr__(self) -> str:
+        return f"Joint({self.name!r}, id={self._id})"
+
+
+class FixedFrame(_Joint):
+    """A named frame welded to a movable joint's link (a folded URDF fixed joint, a tool point):
+    ``parent_name`` names the carrying joint, ``get_transformation_matrix_hom()`` is the 4x4 pose of
+    the frame in that joint's LINK frame (the frame ``get_Xmat_hom_Func_by_id`` chains)."""
+
+    def __init__(self, fid: int, name: str, parent_name: str, T: np.ndarray):
+        super().__init__(fid, name)
+        self.parent_name = parent_name
+        self._T = np.asarray(T, dtype=np.float64).reshape(4, 4).copy()
+
+    def get_transformation_matrix_hom(self) -> np.matrix:
+        return np.matrix(self._T)
+
+    def __repr__(self) -> str:
+        return f"FixedFrame({self.name!r}, id={self._id}, on {self.parent_name!r})"
 
 
 class Robot:
@@ -110,7 +144,9 @@ class Robot:
 
     floating_base = False
 
-    def __init__(self, name: str, links: List[Link]):
+    def __init__(self, name: str, links: List[Link], fixed_frames: Sequence = ()):
+        """``fixed_frames``: ``(name, carrying joint (body id or link name), 4x4 pose in that joint's link frame)``
+        triples -- the named fixed frames `end_effector_pose` can select (``get_fixed_joint_by_name``)."""
         self.name = name
         self.links = list(links)
         n = len(self.links)
@@ -144,6 +180,69 @@ class Robot:
             p = self._parent[i]
             if p >= 0:
                 self._subtree[p] = sorted(self._subtree[p] + self._subtree[i])
+        # ---- kinematics getters (RBDReference.end_effector_pose*, :190-386); nothing here is packed ----
+        self._by_name = {}
+        for i, l in enumerate(self.links):
+            if l.name in self._by_name:
+                raise ValueError(f"two bodies are named {l.name!r}")
+            self._by_name[l.name] = i
+        self._Thom: List[np.ndarray] = []           # [4, 4] pose of body i's frame at q = 0 in its parent's BODY frame
+        self._Fin: List[np.ndarray] = []            # [3, 3] orientation of body i's frame in its link frame
+        for i, l in enumerate(self.links):
+            Xt = self._Xtree[i]
+            E = Xt[:3, :3]
+            rx = -E.T @ Xt[3:, :3]
+            T = np.eye(4)
+            T[:3, :3] = E.T
+            T[:3, 3] = (rx[2, 1], rx[0, 2], rx[1, 0])
+            self._Thom.append(T)
+            self._Fin.append(np.eye(3) if l.frame is None else np.asarray(l.frame, dtype=np.float64).reshape(3, 3).copy())
+        self._fixed: List[FixedFrame] = []
+        for k, ff in enumerate(fixed_frames):
+            nm, carrier, T = ff
+            if carrier is None or (isinstance(carrier, (int, np.integer)) and int(carrier) < 0):
+                raise ValueError(f"fixed frame {nm!r} hangs on the world: it needs a carrying movable joint "
+                                 "(the reference addresses a fixed frame through its parent joint, RBDReference.py:263-273)")
+            cid = int(carrier) if isinstance(carrier, (int, np.integer)) else self._by_name.get(carrier)
+            if cid is None or not (0 <= cid < n):
+                raise ValueError(f"fixed frame {nm!r}: unknown carrying joint {carrier!r}")
+            if nm in self._by_name or any(f.name == nm for f in self._fixed):
+                raise ValueError(f"fixed frame {nm!r}: the name is taken")
+            T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+            if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+                raise ValueError(f"fixed frame {nm!r}: not a homogeneous transform (last row must be 0 0 0 1)")
+            self._fixed.append(FixedFrame(k, nm, self.links[cid].name, T))
+        self._Xhom = [self._make_xhom(i, False) for i in range(n)]
+        self._dXhom = [self._make_xhom(i, True) for i in range(n)]
+
+    def _make_xhom(self, i: int, deriv: bool) -> Callable[[float], np.matrix]:
+        """``Xmat_hom_i(q)`` (pose of link i's frame in its parent link's frame, world for a root) or its derivative:
+        ``C_p T_tree_i T_J(q) C_i^-1`` with ``C = [[frame, 0], [0, 1]]`` (identity for the world)."""
+        l = self.links[i]
+        p = self._parent[i]
+        L = np.eye(4)
+        if p >= 0:
+            L[:3, :3] = self._Fin[p]
+        L = L @ self._Thom[i]
+        Rinv = np.eye(4)
+        Rinv[:3, :3] = self._Fin[i].T
+        k = l.axis
+        a, b = (k + 1) % 3, (k + 2) % 3
+        rev = l.jtype == "revolute"
+
+        def f(q, _L=L, _Ri=Rinv):
+            q = float(q)
+            J = np.zeros((4, 4)) if deriv else np.eye(4)
+            if rev:
+                c, s = (math.cos(q), math.sin(q)) if math.isfinite(q) else (float("nan"), float("nan"))
+                if deriv:                       # d/dq of the active rotation about e_k
+                    J[a, a], J[a, b], J[b, a], J[b, b] = -s, -c, c, -s
+                else:
+                    J[a, a], J[a, b], J[b, a], J[b, b] = c, -s, s, c
+            else:
+                J[k, 3] = 1.0 if deriv else q
+            return np.matrix(_L @ J @ _Ri)
+        return f
 
     @staticmethod
     def _make_xfunc(jtype: str, axis: int, Xt: np.ndarray) -> Callable[[float], np.ndarray]:
@@ -196,6 +295,52 @@ class Robot:
 
     def get_damping_by_id(self, i: int) -> float:
         return float(self.links[i].damping)
+
+    # ---- getters of the kinematics methods (RBDReference.py:190-386) ------------------------------------------------
+    def get_num_joints(self) -> int:
+        return self._n
+
+    def get_leaf_nodes(self) -> List[int]:
+        """Bodies without children, ascending."""
+        return [i for i in range(self._n) if len(self._subtree[i]) == 1]
+
+    def get_ancestors_by_id(self, i: int) -> List[int]:
+        """Strict ancestors of body i, root first."""
+        out = []
+        p = self._parent[i]
+        while p != -1:
+            out.append(p)
+            p = self._parent[p]
+        return out[::-1]
+
+    def get_joint_by_name(self, name: str):
+        i = self._by_name.get(name)
+        return None if i is None else _Joint(i, name)
+
+    def get_fixed_joint_by_name(self, name: str):
+        for f in self._fixed:
+            if f.name == name:
+                return f
+        return None
+
+    def get_fixed_joint_by_id(self, i: int):
+        return self._fixed[i]
+
+    def get_fixed_joints(self) -> List["FixedFrame"]:
+        return list(self._fixed)
+
+    def get_Xmat_hom_Func_by_id(self, i: int) -> Callable[[float], np.matrix]:
+        """``q -> 4x4 np.matrix``: pose of link i's frame in its parent link's frame (the world for a root).  For
+        ``X = plux(E, r)`` of a body whose link frame is its body frame: ``[[E^T, r], [0, 1]]``."""
+        return self._Xhom[i]
+
+    def get_dXmat_hom_Func_by_id(self, i: int) -> Callable[[float], np.matrix]:
+        return self._dXhom[i]
+
+    def link_frame_in_body(self, i: int) -> np.ndarray:
+        """3x3 orientation of body i's link frame in its body frame (identity unless the URDF loader rotated the
+        body frame onto the joint axis)."""
+        return self._Fin[i].T.copy()
 
     def __repr__(self) -> str:
         return f"Robot({self.name!r}, n={self._n})"

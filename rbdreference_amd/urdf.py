@@ -14,6 +14,10 @@ revolute / continuous / prismatic / fixed with ``<origin>``, ``<axis>`` (any dir
 folded: the child link's inertia is added to the body that carries it and its children are re-hung
 with the composed transform.  A joint axis that is not a positive coordinate axis is handled by
 rotating the body frame so that it becomes one (the hot path assumes ``S = e_k``, Appendix A).
+The body frame of such a joint is then not its URDF link frame: the rotation is recorded per body
+(``Link.frame``), so ``Robot.get_Xmat_hom_Func_by_id`` chains the URDF link frames.  Folded fixed joints
+stay addressable as named fixed frames (``Robot.get_fixed_joint_by_name``) posed in the carrying joint's
+link frame; a fixed joint hung on the root link has no carrying joint and is not recorded.
 Not supported (rejected with a ValueError): floating / planar / mimic joints, several root links,
 kinematic loops, movable leaf bodies without mass.
 """
@@ -91,7 +95,8 @@ def loads_urdf(text: str, name: Optional[str] = None) -> Robot:
     if len(roots) != 1:
         raise ValueError(f"expected exactly one root link, found {roots}")
 
-    bodies: List[dict] = []          # parent, jtype, axis, E, r, damping, name, I (6x6 accumulated)
+    bodies: List[dict] = []          # parent, jtype, axis, E, r, damping, name, I (6x6 accumulated), frame
+    fixed: List[tuple] = []          # (name, carrying body, 4x4 pose in its link frame): folded fixed joints
 
     def add_inertia(link_el, body: int, E_cl: np.ndarray, r_cl: np.ndarray):
         """Add the link's inertia to body `body`; link coords = E_cl (x_body - r_cl)."""
@@ -119,6 +124,10 @@ def loads_urdf(text: str, name: Optional[str] = None) -> Robot:
             r = r_cl + E_cl.T @ r_o
             child = j.find("child").get("link")
             if jt == "fixed":
+                if body >= 0:        # a named frame on the carrying body, posed in that body's LINK frame
+                    F = bodies[body]["frame"]
+                    T = np.eye(4); T[:3, :3] = F @ E.T; T[:3, 3] = F @ r
+                    fixed.append((j.get("name"), body, T))
                 walk(child, body, E, r)
                 continue
             if jt in ("revolute", "continuous"):
@@ -133,7 +142,7 @@ def loads_urdf(text: str, name: Optional[str] = None) -> Robot:
                 raise ValueError(f"joint {j.get('name')!r}: zero axis")
             A, k = _axis_frame(a)
             dyn = j.find("dynamics")
-            bodies.append(dict(parent=body, jtype=kind, axis=k, E=_snap(A @ E), r=r, name=j.get("name"),
+            bodies.append(dict(parent=body, jtype=kind, axis=k, E=_snap(A @ E), r=r, name=j.get("name"), frame=A.T,
                                damping=float(dyn.get("damping", 0.0)) if dyn is not None else 0.0,
                                I=np.zeros((6, 6))))
             walk(child, len(bodies) - 1, A.T, np.zeros(3))       # child-link coords = A^T body coords
@@ -160,8 +169,8 @@ def loads_urdf(text: str, name: Optional[str] = None) -> Robot:
             Ic = I[:3, :3] - m * (C @ C.T)
         out.append(Link(b["name"], b["parent"], b["axis"], tuple(b["r"]), (0.0, 0.0, 0.0), m, tuple(com),
                         (Ic[0, 0], Ic[1, 1], Ic[2, 2], Ic[0, 1], Ic[0, 2], Ic[1, 2]), b["damping"], b["jtype"],
-                        rot=b["E"]))
-    return Robot(rname, out)
+                        rot=b["E"], frame=b["frame"]))
+    return Robot(rname, out, fixed_frames=fixed)
 
 
 def load_urdf(path: str, name: Optional[str] = None) -> Robot:
