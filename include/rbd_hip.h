@@ -266,6 +266,21 @@ int rbd_ee_pose_f32(const float* q, int64_t B, const int32_t* site_body, const d
 int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset,
                     int n_sites, double* pose, double* dpose, void* stream);
 
+/* RBDReference.second_order_idsva_parallel                                                        (RBDReference.py:1387-1604)
+ * Fixed-base robots; a floating-base library returns RBD_ERR_UNSUPPORTED.
+ *   q, qd, qdd : [B, n] device
+ *   out        : [B, 4, n, n, n] = d2tau_dq, d2tau_dqd, d2tau_dvdq, dM_dq, every entry written (zeros included)
+ *                d2tau_dq[i][j][k] = d2 c_i / dq_j dq_k,  d2tau_dqd[i][j][k] = d2 c_i / dqd_j dqd_k,
+ *                d2tau_dvdq[i][j][k] = d (dc_dqd[i][j]) / dq_k,  dM_dq[i][j][k] = d H_ij / dq_k
+ *                (c = rnea(q, qd, qdd, gravity), H = crba(q)).  The composite-force sweep adds the child's force (the
+ *                reference's :1448 adds f[:, pi + 1]): on a branched robot d2tau_dq is the true derivative where the
+ *                reference's is not; elsewhere the two agree.
+ * Arguments are checked before anything touches the GPU; B == 0 is a no-op. */
+int rbd_second_order_idsva_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B, float* out,
+                               void* stream);
+int rbd_second_order_idsva_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B,
+                               double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "rbd_aba_f32", "rbd_aba_f64",
     "rbd_minv_bpass_f32", "rbd_minv_bpass_f64", "rbd_minv_fpass_f32", "rbd_minv_fpass_f64",
     "rbd_ee_pose_f32", "rbd_ee_pose_f64",
+    "rbd_second_order_idsva_f32", "rbd_second_order_idsva_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -117,6 +118,10 @@ def _declare(lib):
         f = getattr(lib, f"rbd_ee_pose_{sfx}")
         f.restype = c_int
         f.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    for sfx, ct in (("f32", c_float), ("f64", c_double)):
+        f = getattr(lib, f"rbd_second_order_idsva_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, ct, c_int64, c_void_p, c_void_p]
     lib.rbd_minv_workspace_bytes.restype = c_size_t
     lib.rbd_minv_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_fd_workspace_bytes.restype = c_size_t

@@ -780,6 +780,33 @@ class RBDReference:
         d = self._ret(d, unb, is_np)
         return d[..., :n], d[..., n:]
 
+    # ---- second-order inverse-dynamics derivatives (RBDReference.py:1387-1604): rbd_second_order_idsva --------------
+    def second_order_idsva_parallel(self, q, qd, qdd, GRAVITY=-9.81):
+        """RBDReference.second_order_idsva_parallel (``RBDReference.py:1387-1604``) -> ``(d2tau_dq, d2tau_dqd, d2tau_dvdq,
+        dM_dq)``, each ``(n, n, n)`` per configuration, with ``c = rnea(q, qd, qdd, GRAVITY)[0]`` and ``H = crba(q)``:
+        ``d2tau_dq[i, j, k] = d2 c_i / dq_j dq_k``, ``d2tau_dqd[i, j, k] = d2 c_i / dqd_j dqd_k``,
+        ``d2tau_dvdq[i, j, k] = d (dc_dqd[i, j]) / dq_k`` and ``dM_dq[i, j, k] = d H_ij / dq_k``, zeros included.
+
+        These are the true derivatives.  The reference's composite-force sweep adds ``f[:, pi + 1]`` to the parent
+        (:1448); this method adds the child's force.  On robots whose non-root bodies all have parent ``i - 1`` the two
+        agree; on a branched robot the reference's ``d2tau_dq`` is not the derivative and this one differs from it (the
+        other three outputs do not read ``f``).  Fixed-base robots only, as in the reference.
+
+        ``q [n]`` -> four ``(n, n, n)`` arrays (float64 ndarrays for numpy inputs); ``q [B, n]`` -> four ``[B, n, n, n]``
+        views of one ``[B, 4, n, n, n]`` buffer."""
+        if self.model.floating:
+            raise NotImplementedError("second_order_idsva_parallel: fixed-base robots only (the reference indexes q per "
+                                      "body, RBDReference.py:1387-1604)")
+        (q, qd, qdd), unb, is_np, dev, dt = self._prep(q, qd, qdd)
+        B, n = q.shape[0], self.n
+        with torch.cuda.device(dev):
+            out = torch.empty((B, 4, n, n, n), device=dev, dtype=dt)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_second_order_idsva", dt)(
+                self._ptr(q), self._ptr(qd), self._ptr(qdd), float(GRAVITY), B, self._ptr(out), st))
+        out = self._ret(out, unb, is_np)
+        return out[..., 0, :, :, :], out[..., 1, :, :, :], out[..., 2, :, :, :], out[..., 3, :, :, :]
+
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):
         """Site table of a selection, resolved once and cached: ``(chunks of (site_body int32 [k], site_T float64 [k, 12]),

@@ -64,7 +64,8 @@ def _sources_digest(m: PackedModel, flags) -> str:
 
 
 TRANSLATION_UNITS = ["COMMON", "RNEA_F32", "RNEA_F64", "GRAD_F32", "GRAD_F64", "GRADN_F32", "GRADN_F64", "MINV_F32", "MINV_F64",
-                     "FD_F32", "FD_F64", "PASS_F32", "PASS_F64", "EE_F32", "EE_F64"]
+                     "FD_F32", "FD_F64", "PASS_F32", "PASS_F64", "EE_F32", "EE_F64",
+                     "SO_F32", "SO_F64"]
 # floating-base robots: COMMON from rbd_kernels.hip + the two units of rbd_fb_kernels.hip
 FB_TRANSLATION_UNITS = ["COMMON", "FB_F32", "FB_F64"]
 class _PrioritySlots:
@@ -262,9 +263,10 @@ FAMILIES = {           # family -> units (suffix _F32 / _F64 appended)
     "fd": ["FD", "RNEA", "MINV"],
     "pass": ["PASS"],
     "ee": ["EE"],                               # rbd_ee_pose (end-effector kinematics)
+    "so": ["SO"],                               # rbd_second_order_idsva
 }
 _FAST_UNITS = {"GRAD", "GRADN", "RNEA"}
-_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE"]
+_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE", "SO"]
 
 
 def family_of(symbol: str, has_qdd: bool = True) -> str:
@@ -281,6 +283,8 @@ def family_of(symbol: str, has_qdd: bool = True) -> str:
         return "fd"
     if symbol == "rbd_ee_pose":
         return "ee"
+    if symbol == "rbd_second_order_idsva":
+        return "so"
     return "pass"
 
 

@@ -49,6 +49,8 @@
 #define RBD_TU_PASS_F64 1
 #define RBD_TU_EE_F32 1
 #define RBD_TU_EE_F64 1
+#define RBD_TU_SO_F32 1
+#define RBD_TU_SO_F64 1
 #endif
 
 // Which kernel families this unit needs (everything it does not need is dropped by the preprocessor,
@@ -71,6 +73,9 @@
 #endif
 #if defined(RBD_TU_EE_F32) || defined(RBD_TU_EE_F64)
 #define RBD_NEED_EE 1
+#endif
+#if defined(RBD_TU_SO_F32) || defined(RBD_TU_SO_F64)
+#define RBD_NEED_SO 1
 #endif
 #include "rbd_spatial.h"
 
@@ -2069,6 +2074,9 @@ __global__ __launch_bounds__(64 * MINV_COLS_W, MINV_COLS_MIN_WAVES) void minv_co
 #ifdef RBD_NEED_EE
 #include "rbd_ee.h"
 #endif
+#ifdef RBD_NEED_SO
+#include "rbd_idsva_so.h"
+#endif
 namespace rbdk {
 #ifdef RBD_NO_MINV_LANE
 template <class T>
@@ -2983,6 +2991,26 @@ int ee_launch(const T* q, int64_t B, const int32_t* site_body, const double* sit
 }
 #endif  // RBD_NEED_EE
 
+#ifdef RBD_NEED_SO
+// rbd_second_order_idsva: out [B, 4, N, N, N]; arguments checked before anything touches the GPU
+template <class T>
+int so_launch(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, T* out, void* stream) {
+  using namespace rbdk;
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_second_order_idsva: fixed-base robots only");
+  if (B < 0) return fail(RBD_ERR_ARG, "rbd_second_order_idsva: B < 0");
+  if (B == 0) return 0;
+  if (!q || !qd || !qdd || !out) return fail(RBD_ERR_ARG, "rbd_second_order_idsva: q, qd, qdd and out must be non-null");
+  constexpr int G = so_configs_per_block<T>();
+  const int64_t blocks = (B + G - 1) / G;
+  if (blocks > 0x7fffffffLL || B > (int64_t)(INT64_MAX / SO_PER_CFG))
+    return fail(RBD_ERR_ARG, "rbd_second_order_idsva: B too large");
+  hipLaunchKernelGGL(so_idsva_kernel<T>, dim3((unsigned)blocks), dim3(SO_THREADS), 0, (hipStream_t)stream, q, qd, qdd,
+                     gravity, (long long)B, out);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "rbd_second_order_idsva launch");
+}
+#endif  // RBD_NEED_SO
+
 #if defined(RBD_TU_PASS_F32) || defined(RBD_TU_PASS_F64)
 // ---- per-pass entry points (rbd_passes.h) ------------------------------------------------------------
 int pass_blocks(int64_t B, const char* who, unsigned* blocks) {
@@ -3315,6 +3343,18 @@ int rbd_ee_pose_f32(const float* q, int64_t B, const int32_t* site_body, const d
   RbdStreamDevice sd_(stream); return ee_launch<float>(q, B, site_body, site_T, offset, n_sites, pose, dpose, stream);
 }
 #endif
+#ifdef RBD_TU_SO_F32
+int rbd_second_order_idsva_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B, float* out,
+                               void* stream) {
+  RbdStreamDevice sd_(stream); return so_launch<float>(q, qd, qdd, gravity, B, out, stream);
+}
+#endif
+#ifdef RBD_TU_SO_F64
+int rbd_second_order_idsva_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B, double* out,
+                               void* stream) {
+  RbdStreamDevice sd_(stream); return so_launch<double>(q, qd, qdd, gravity, B, out, stream);
+}
+#endif
 #ifdef RBD_TU_EE_F64
 int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
                     double* pose, double* dpose, void* stream) {
@@ -3357,6 +3397,14 @@ int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const 
   int rbd_minv_fpass_##SFX(const T*, int64_t, T*, T*, const T*, const T*, void*) RBD_STUB_BODY("rbd_minv_fpass")
 #define RBD_STUBS_EE(SFX, T)                                                                                                     \
   int rbd_ee_pose_##SFX(const T*, int64_t, const int32_t*, const double*, const double*, int, T*, T*, void*) RBD_STUB_BODY("rbd_ee_pose")
+#define RBD_STUBS_SO(SFX, T)                                                                                                     \
+  int rbd_second_order_idsva_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) RBD_STUB_BODY("rbd_second_order_idsva")
+#ifdef RBD_STUB_SO_F32
+RBD_STUBS_SO(f32, float)
+#endif
+#ifdef RBD_STUB_SO_F64
+RBD_STUBS_SO(f64, double)
+#endif
 #ifdef RBD_STUB_EE_F32
 RBD_STUBS_EE(f32, float)
 #endif

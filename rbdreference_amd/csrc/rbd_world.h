@@ -289,7 +289,8 @@ struct WState {
   T R[3][3], p[3], v[6], a[6];   // body -> world rotation, origin, spatial velocity / acceleration (world frame)
 };
 
-// parent(J) -> J  (:1413-1434); for a root the incoming state is ignored
+// parent(J) -> J  (:1413-1434); for a root the incoming state is ignored.  Revolute and prismatic joints (ws_up:
+// revolute only)
 template <int J, class T>
 RBD_DEV void ws_down(WState<T>& s, const JTrig<T>& g, T qd, T qdd, T grav, T (&Sv)[6], T (&Pd)[6], T (&Pdd)[6]) {
   constexpr int k = AXIS[J], ka = (k + 1) % 3, kb = (k + 2) % 3;
@@ -328,22 +329,32 @@ RBD_DEV void ws_down(WState<T>& s, const JTrig<T>& g, T qd, T qdd, T grav, T (&S
       pn[r] = acc;
     }
   });
-  sfor<0, 3>([&](auto R_) {
-    constexpr int r = decltype(R_)::value;
-    s.R[r][ka] = fma_(g.c, Tm[r][ka], g.s * Tm[r][kb]);
-    s.R[r][kb] = fma_(g.c, Tm[r][kb], -(g.s * Tm[r][ka]));
-    s.R[r][k] = Tm[r][k];
-    s.p[r] = pn[r];
-  });
-  const T ang[3] = {s.R[0][k], s.R[1][k], s.R[2][k]};
-  T sl[3];
-  cross3(s.p, ang, sl);
-  sfor<0, 3>([&](auto R_) { constexpr int r = decltype(R_)::value; Sv[r] = ang[r]; Sv[3 + r] = sl[r]; });
+  if constexpr (JTYPE[J] == 0) {
+    sfor<0, 3>([&](auto R_) {
+      constexpr int r = decltype(R_)::value;
+      s.R[r][ka] = fma_(g.c, Tm[r][ka], g.s * Tm[r][kb]);
+      s.R[r][kb] = fma_(g.c, Tm[r][kb], -(g.s * Tm[r][ka]));
+      s.R[r][k] = Tm[r][k];
+      s.p[r] = pn[r];
+    });
+    const T ang[3] = {s.R[0][k], s.R[1][k], s.R[2][k]};
+    T sl[3];
+    cross3(s.p, ang, sl);
+    sfor<0, 3>([&](auto R_) { constexpr int r = decltype(R_)::value; Sv[r] = ang[r]; Sv[3 + r] = sl[r]; });
+  } else {                                       // prismatic (g.s = q): the frame slides by q along its axis k, S = [0; axis]
+    sfor<0, 3>([&](auto R_) {
+      constexpr int r = decltype(R_)::value;
+      sfor<0, 3>([&](auto C_) { constexpr int c = decltype(C_)::value; s.R[r][c] = Tm[r][c]; });
+      s.p[r] = fma_(g.s, Tm[r][k], pn[r]);
+      Sv[r] = T(0);
+      Sv[3 + r] = Tm[r][k];
+    });
+  }
   if constexpr (root) {
     sfor<0, 6>([&](auto R_) { Pd[decltype(R_)::value] = T(0); });
     Pdd[0] = T(0); Pdd[1] = T(0); Pdd[2] = T(0);
-    Pdd[3] = grav * ang[1];
-    Pdd[4] = -(grav * ang[0]);
+    Pdd[3] = JTYPE[J] == 0 ? grav * Sv[1] : T(0);   // crm(a_base) S: zero for a pure translation
+    Pdd[4] = JTYPE[J] == 0 ? -(grav * Sv[0]) : T(0);
     Pdd[5] = T(0);
     sfor<0, 6>([&](auto R_) {
       constexpr int r = decltype(R_)::value;
