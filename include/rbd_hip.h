@@ -281,6 +281,32 @@ int rbd_second_order_idsva_f32(const float* q, const float* qd, const float* qdd
 int rbd_second_order_idsva_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B,
                                double* out, void* stream);
 
+/* RBDReference.fdsva_so: second derivatives of forward dynamics                                  (RBDReference.py:1606-1631)
+ * Fixed-base robots; a floating-base library returns RBD_ERR_UNSUPPORTED.
+ *   q, qd, u : [B, n] device
+ *   out      : [B, 4, n, n, n] = daba_dqdq, daba_dvdq, daba_dvdv, daba_dtdq, every entry written (zeros included).  With
+ *              qdd = forward_dynamics(q, qd, u), [fd_dq | fd_dqd] = forward_dynamics_grad(q, qd, u), Minv = minv(q) and
+ *              (d2tau_dq, d2tau_dqd, d2tau_dvdq, dM_dq) = second_order_idsva(q, qd, qdd), all at the given gravity:
+ *                daba_dqdq[i][j][k] = -sum_l Minv[i][l] (d2tau_dq[l][j][k] + sum_m dM_dq[l][m][k] fd_dq[m][j]
+ *                                                                            + sum_m dM_dq[l][m][j] fd_dq[m][k])
+ *                daba_dvdq[i][j][k] = -sum_l Minv[i][l] (d2tau_dvdq[l][j][k] + sum_m dM_dq[l][m][k] fd_dqd[m][j])
+ *                daba_dvdv[i][j][k] = -sum_l Minv[i][l] d2tau_dqd[l][j][k]
+ *                daba_dtdq[i][j][k] = -sum_l Minv[i][l] sum_m dM_dq[l][m][k] Minv[m][j]  (= d Minv[i][j] / dq_k)
+ *              The second-order inverse-dynamics tensors are this library's (true derivatives on branched robots, see
+ *              above), so daba_dqdq differs from the reference's on branched robots.  fd_dq is forward_dynamics_grad's:
+ *              on a robot with prismatic joints it is not the q-derivative of qdd (the reference's rnea_grad, reproduced
+ *              for parity), and daba_dqdq then is not the second derivative.  One gravity in every stage (the reference
+ *              evaluates forward dynamics at -9.81 whatever GRAVITY is).
+ *   ws       : device scratch of at least the bytes the workspace query below reports for (B, elem_size), 16-byte
+ *              aligned; every intermediate lives there.  Everything runs on `stream`.
+ * Arguments are checked before anything touches the GPU (null pointer, B < 0, B too large, workspace too small:
+ * RBD_ERR_ARG); B == 0 is a no-op. */
+size_t rbd_fdsva_so_workspace_bytes(int64_t B, int elem_size);
+int rbd_fdsva_so_f32(const float* q, const float* qd, const float* u, float gravity, int64_t B, float* out, void* ws,
+                     size_t ws_bytes, void* stream);
+int rbd_fdsva_so_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B, double* out, void* ws,
+                     size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "rbd_minv_bpass_f32", "rbd_minv_bpass_f64", "rbd_minv_fpass_f32", "rbd_minv_fpass_f64",
     "rbd_ee_pose_f32", "rbd_ee_pose_f64",
     "rbd_second_order_idsva_f32", "rbd_second_order_idsva_f64",
+    "rbd_fdsva_so_workspace_bytes", "rbd_fdsva_so_f32", "rbd_fdsva_so_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -122,6 +123,11 @@ def _declare(lib):
         f = getattr(lib, f"rbd_second_order_idsva_{sfx}")
         f.restype = c_int
         f.argtypes = [c_void_p, c_void_p, c_void_p, ct, c_int64, c_void_p, c_void_p]
+        f = getattr(lib, f"rbd_fdsva_so_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, ct, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.rbd_fdsva_so_workspace_bytes.restype = c_size_t
+    lib.rbd_fdsva_so_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_minv_workspace_bytes.restype = c_size_t
     lib.rbd_minv_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_fd_workspace_bytes.restype = c_size_t

@@ -807,6 +807,40 @@ class RBDReference:
         out = self._ret(out, unb, is_np)
         return out[..., 0, :, :, :], out[..., 1, :, :, :], out[..., 2, :, :, :], out[..., 3, :, :, :]
 
+    # ---- second-order forward-dynamics derivatives (RBDReference.py:1606-1631): rbd_fdsva_so ---------------------------
+    def fdsva_so(self, q, qd, u, GRAVITY=-9.81):
+        """RBDReference.fdsva_so (``RBDReference.py:1606-1631``) -> ``(daba_dqdq, daba_dvdq, daba_dvdv, daba_dtdq)``, each
+        ``(n, n, n)`` per configuration: the second derivatives of ``qdd = forward_dynamics(q, qd, u)``,
+        ``d2 qdd_i / dq_j dq_k``, ``d (qdd_dqd[i, j]) / dq_k``, ``d2 qdd_i / dqd_j dqd_k`` and ``d Minv[i, j] / dq_k``.
+
+        It is the reference's composition (:1625-1629) of this package's own ``minv``, ``forward_dynamics_grad`` and
+        ``second_order_idsva_parallel`` at ``qdd``, contracted in one HIP kernel.  Three things follow.  On branched
+        robots ``daba_dqdq`` differs from the reference's, because ``d2tau_dq`` does (the corrected composite-force
+        index, see ``second_order_idsva_parallel``); the other three outputs match it.  On robots with prismatic joints
+        ``daba_dqdq`` is not the second derivative: it inherits ``forward_dynamics_grad``'s ``qdd_dq``, which reproduces
+        the reference's ``rnea_grad`` and is not the q-derivative for such joints.  And ``GRAVITY`` is used in every
+        stage (the reference evaluates forward dynamics at -9.81 whatever it is given).  Fixed-base robots only.
+
+        ``q [n]`` -> four ``(n, n, n)`` arrays (float64 ndarrays for numpy inputs); ``q [B, n]`` -> four ``[B, n, n, n]``
+        views of one ``[B, 4, n, n, n]`` buffer."""
+        if self.model.floating:
+            raise NotImplementedError("fdsva_so: fixed-base robots only (the reference's fdsva_so calls "
+                                      "second_order_idsva_parallel, RBDReference.py:1606-1631)")
+        (q, qd, u), unb, is_np, dev, dt = self._prep(q, qd, u)
+        B, n = q.shape[0], self.n
+        esz = 4 if dt == torch.float32 else 8
+        sfx = "f32" if esz == 4 else "f64"
+        with torch.cuda.device(dev):
+            out = torch.empty((B, 4, n, n, n), device=dev, dtype=dt)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib = self._lib.resolve("rbd_fdsva_so", sfx)    # ONE resolution: workspace size and entry point from the same library
+            wsb = int(lib.rbd_fdsva_so_workspace_bytes(B, esz))
+            ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
+            self._lib.check(getattr(lib, f"rbd_fdsva_so_{sfx}")(
+                self._ptr(q), self._ptr(qd), self._ptr(u), float(GRAVITY), B, self._ptr(out), ws.data_ptr(), wsb, st))
+        out = self._ret(out, unb, is_np)
+        return out[..., 0, :, :, :], out[..., 1, :, :, :], out[..., 2, :, :, :], out[..., 3, :, :, :]
+
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):
         """Site table of a selection, resolved once and cached: ``(chunks of (site_body int32 [k], site_T float64 [k, 12]),

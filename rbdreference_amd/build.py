@@ -65,7 +65,7 @@ def _sources_digest(m: PackedModel, flags) -> str:
 
 TRANSLATION_UNITS = ["COMMON", "RNEA_F32", "RNEA_F64", "GRAD_F32", "GRAD_F64", "GRADN_F32", "GRADN_F64", "MINV_F32", "MINV_F64",
                      "FD_F32", "FD_F64", "PASS_F32", "PASS_F64", "EE_F32", "EE_F64",
-                     "SO_F32", "SO_F64"]
+                     "SO_F32", "SO_F64", "FDSO_F32", "FDSO_F64"]
 # floating-base robots: COMMON from rbd_kernels.hip + the two units of rbd_fb_kernels.hip
 FB_TRANSLATION_UNITS = ["COMMON", "FB_F32", "FB_F64"]
 class _PrioritySlots:
@@ -264,9 +264,10 @@ FAMILIES = {           # family -> units (suffix _F32 / _F64 appended)
     "pass": ["PASS"],
     "ee": ["EE"],                               # rbd_ee_pose (end-effector kinematics)
     "so": ["SO"],                               # rbd_second_order_idsva
+    "fdso": ["FDSO", "SO", "FD", "RNEA", "MINV"],  # rbd_fdsva_so: its contraction + the three entry points it launches
 }
 _FAST_UNITS = {"GRAD", "GRADN", "RNEA"}
-_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE", "SO"]
+_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE", "SO", "FDSO"]
 
 
 def family_of(symbol: str, has_qdd: bool = True) -> str:
@@ -285,6 +286,8 @@ def family_of(symbol: str, has_qdd: bool = True) -> str:
         return "ee"
     if symbol == "rbd_second_order_idsva":
         return "so"
+    if symbol in ("rbd_fdsva_so", "rbd_fdsva_so_workspace_bytes"):
+        return "fdso"
     return "pass"
 
 

@@ -51,6 +51,8 @@
 #define RBD_TU_EE_F64 1
 #define RBD_TU_SO_F32 1
 #define RBD_TU_SO_F64 1
+#define RBD_TU_FDSO_F32 1
+#define RBD_TU_FDSO_F64 1
 #endif
 
 // Which kernel families this unit needs (everything it does not need is dropped by the preprocessor,
@@ -76,6 +78,9 @@
 #endif
 #if defined(RBD_TU_SO_F32) || defined(RBD_TU_SO_F64)
 #define RBD_NEED_SO 1
+#endif
+#if defined(RBD_TU_FDSO_F32) || defined(RBD_TU_FDSO_F64)
+#define RBD_NEED_FDSO 1
 #endif
 #include "rbd_spatial.h"
 
@@ -2077,6 +2082,9 @@ __global__ __launch_bounds__(64 * MINV_COLS_W, MINV_COLS_MIN_WAVES) void minv_co
 #ifdef RBD_NEED_SO
 #include "rbd_idsva_so.h"
 #endif
+#ifdef RBD_NEED_FDSO
+#include "rbd_fdsva_so.h"
+#endif
 namespace rbdk {
 #ifdef RBD_NO_MINV_LANE
 template <class T>
@@ -2844,6 +2852,81 @@ struct FdWorkspace {
   }
 };
 
+// rbd_fdsva_so: the caller's workspace holds the forward_dynamics_grad workspace (minv's scratch is its first part and is
+// reused by the dense minv that follows), then qdd [B, N], [fd_dq | fd_dqd] [B, N, 2N], Minv [B, N, N] and the
+// second_order_idsva tensors [B, 4, N, N, N]
+template <class T>
+struct FdsoWorkspace {
+  size_t fd_bytes, off_qdd, off_fd, off_minv, off_so, total;
+  explicit FdsoWorkspace(int64_t B) {
+    using namespace rbdk;
+    const size_t nn = (size_t)N * N;
+    size_t o = FdWorkspace<T>(B).total;
+    fd_bytes = o;
+    off_qdd = o;  o += align16((size_t)B * N * sizeof(T));
+    off_fd = o;   o += align16((size_t)B * 2 * nn * sizeof(T));
+    off_minv = o; o += align16((size_t)B * nn * sizeof(T));
+    off_so = o;   o += align16((size_t)B * 4 * nn * N * sizeof(T));
+    total = o;
+  }
+};
+// largest B whose workspace and output sizes stay far inside size_t / int64 index arithmetic
+inline int64_t fdso_max_batch() { return (int64_t)(INT64_MAX / (int64_t)(4 * (FdsoWorkspace<double>(1).total + 64))); }
+
+#ifdef RBD_NEED_FDSO
+// rbd_fdsva_so: forward_dynamics_grad (qdd, fd_dq | fd_dqd), dense minv, second_order_idsva at that qdd -- the existing
+// entry points, on the caller's stream -- then the contraction of rbd_fdsva_so.h.  Arguments are checked before any launch.
+template <class T>
+int fdso_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* out, void* workspace, size_t wsb, void* stream) {
+  using namespace rbdk;
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_fdsva_so: fixed-base robots only");
+  if (B < 0) return fail(RBD_ERR_ARG, "rbd_fdsva_so: B < 0");
+  if (B == 0) return 0;
+  if (!q || !qd || !u || !out) return fail(RBD_ERR_ARG, "rbd_fdsva_so: q, qd, u and out must be non-null");
+  constexpr int C = fdso_cfgs();
+  if (B > fdso_max_batch() || (B + C - 1) / C > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_fdsva_so: B too large");
+  const int64_t blocks = (B + C - 1) / C;
+  const FdsoWorkspace<T> L(B);
+  if (!workspace || wsb < L.total) return fail(RBD_ERR_ARG, "rbd_fdsva_so: workspace missing or smaller than rbd_fdsva_so_workspace_bytes()");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(RBD_ERR_ARG, "rbd_fdsva_so: workspace must be 16-byte aligned");
+  if constexpr (N > FDSO_MAX_N) {
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_fdsva_so: robots of more than 32 bodies are not supported (one thread per (j, k) column)");
+  } else {
+    char* w = reinterpret_cast<char*>(workspace);
+    T* qdd = reinterpret_cast<T*>(w + L.off_qdd);
+    T* fd = reinterpret_cast<T*>(w + L.off_fd);
+    T* Mi = reinterpret_cast<T*>(w + L.off_minv);
+    T* so = reinterpret_cast<T*>(w + L.off_so);
+    int rc;
+    if constexpr (sizeof(T) == 4) {
+      if ((rc = rbd_forward_dynamics_grad_f32((const float*)q, (const float*)qd, (const float*)u, (float)gravity, B, (float*)qdd, (float*)fd, w, L.fd_bytes, stream)) != 0) return rc;
+      if ((rc = rbd_minv_f32((const float*)q, B, 1, (float*)Mi, w, L.fd_bytes, stream)) != 0) return rc;
+      if ((rc = rbd_second_order_idsva_f32((const float*)q, (const float*)qd, (const float*)qdd, (float)gravity, B, (float*)so, stream)) != 0) return rc;
+    } else {
+      if ((rc = rbd_forward_dynamics_grad_f64((const double*)q, (const double*)qd, (const double*)u, (double)gravity, B, (double*)qdd, (double*)fd, w, L.fd_bytes, stream)) != 0) return rc;
+      if ((rc = rbd_minv_f64((const double*)q, B, 1, (double*)Mi, w, L.fd_bytes, stream)) != 0) return rc;
+      if ((rc = rbd_second_order_idsva_f64((const double*)q, (const double*)qd, (const double*)qdd, (double)gravity, B, (double*)so, stream)) != 0) return rc;
+    }
+    const dim3 grid((unsigned)blocks), block(fdso_threads());
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int G = fdso_group<T>();
+    if constexpr (G == 4) {
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 15>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+    } else if constexpr (G == 2) {
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 3>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 12>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+    } else {
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 1>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 2>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 4>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+      hipLaunchKernelGGL((fdso_contract_kernel<T, 8>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, "rbd_fdsva_so contraction launch");
+  }
+}
+#endif  // RBD_NEED_FDSO
+
 #ifdef RBD_NEED_FD
 template <class T>
 int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, bool want_grad,
@@ -3171,6 +3254,12 @@ size_t rbd_fd_workspace_bytes(int64_t B, int elem_size) {
   if (elem_size == 8) return FdWorkspace<double>(B).total;
   return 0;
 }
+size_t rbd_fdsva_so_workspace_bytes(int64_t B, int elem_size) {
+  if (B <= 0 || rbdm::FLOATING_BASE || B > fdso_max_batch()) return 0;
+  if (elem_size == 4) return FdsoWorkspace<float>(B).total;
+  if (elem_size == 8) return FdsoWorkspace<double>(B).total;
+  return 0;
+}
 #endif
 #ifdef RBD_TU_RNEA_F32
 int rbd_rnea_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B,
@@ -3355,6 +3444,18 @@ int rbd_second_order_idsva_f64(const double* q, const double* qd, const double* 
   RbdStreamDevice sd_(stream); return so_launch<double>(q, qd, qdd, gravity, B, out, stream);
 }
 #endif
+#ifdef RBD_TU_FDSO_F32
+int rbd_fdsva_so_f32(const float* q, const float* qd, const float* u, float gravity, int64_t B, float* out, void* ws,
+                     size_t ws_bytes, void* stream) {
+  RbdStreamDevice sd_(stream); return fdso_launch<float>(q, qd, u, gravity, B, out, ws, ws_bytes, stream);
+}
+#endif
+#ifdef RBD_TU_FDSO_F64
+int rbd_fdsva_so_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B, double* out, void* ws,
+                     size_t ws_bytes, void* stream) {
+  RbdStreamDevice sd_(stream); return fdso_launch<double>(q, qd, u, gravity, B, out, ws, ws_bytes, stream);
+}
+#endif
 #ifdef RBD_TU_EE_F64
 int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
                     double* pose, double* dpose, void* stream) {
@@ -3399,6 +3500,14 @@ int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const 
   int rbd_ee_pose_##SFX(const T*, int64_t, const int32_t*, const double*, const double*, int, T*, T*, void*) RBD_STUB_BODY("rbd_ee_pose")
 #define RBD_STUBS_SO(SFX, T)                                                                                                     \
   int rbd_second_order_idsva_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) RBD_STUB_BODY("rbd_second_order_idsva")
+#define RBD_STUBS_FDSO(SFX, T)                                                                                                   \
+  int rbd_fdsva_so_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_fdsva_so")
+#ifdef RBD_STUB_FDSO_F32
+RBD_STUBS_FDSO(f32, float)
+#endif
+#ifdef RBD_STUB_FDSO_F64
+RBD_STUBS_FDSO(f64, double)
+#endif
 #ifdef RBD_STUB_SO_F32
 RBD_STUBS_SO(f32, float)
 #endif
