@@ -307,6 +307,29 @@ int rbd_fdsva_so_f32(const float* q, const float* qd, const float* u, float grav
 int rbd_fdsva_so_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B, double* out, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* Forward-simulation rollout: T integration steps of forward dynamics in ONE launch (no counterpart in the reference; a
+ * sampling controller's inner loop).  Fixed-base robots; a floating-base library returns RBD_ERR_UNSUPPORTED.
+ * With qdd_t = aba(q_t, qd_t, u_t, gravity), the articulated-body sweeps of the aba entry point above, one step is
+ *   integrator 0 (semi-implicit Euler): qd_{t+1} = qd_t + dt qdd_t, then q_{t+1} = q_t + dt qd_{t+1}
+ *   integrator 1 (explicit Euler):      q_{t+1} = q_t + dt qd_t,         qd_{t+1} = qd_t + dt qdd_t
+ * (each update one fused multiply-add).  No angle wrapping, joint limits, damping or external forces.
+ *   q0, qd0       : [B, n] device, the state before step 0; never written
+ *   u             : [T, B, n] device (u_shared == 0), or [T, n] (u_shared != 0): one sequence for every row
+ *   q_out, qd_out : trajectory != 0: [T, B, n], slice t = the state AFTER step t + 1 (the initial state is not copied);
+ *                   trajectory == 0: [B, n], the final state only -- nothing but that is written
+ * Everything with a time axis is TIME-MAJOR: a step reads and writes one flat [B, n] tile, coalesced like every other
+ * entry point's, and slice t of a trajectory is a dense [B, n] array that any entry point above takes as it is.
+ * The state stays on chip for all T steps; a step reads n scalars and writes 2 n per row (0 without a trajectory).
+ * Arguments are checked before anything touches the GPU: null pointer, B < 0, T < 0, dt not finite, unknown integrator,
+ * B or B T n too large: RBD_ERR_ARG; a robot whose per-body state exceeds the LDS: RBD_ERR_UNSUPPORTED.  B == 0 or
+ * T == 0 is a no-op (nothing is written, q_out does NOT receive q0). */
+#define RBD_INTEGRATOR_SEMI_IMPLICIT 0
+#define RBD_INTEGRATOR_EULER 1
+int rbd_rollout_f32(const float* q0, const float* qd0, const float* u, int u_shared, float dt, float gravity, int integrator,
+                    int64_t B, int64_t T, float* q_out, float* qd_out, int trajectory, void* stream);
+int rbd_rollout_f64(const double* q0, const double* qd0, const double* u, int u_shared, double dt, double gravity,
+                    int integrator, int64_t B, int64_t T, double* q_out, double* qd_out, int trajectory, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

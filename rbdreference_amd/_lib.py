@@ -21,6 +21,7 @@ RBD_RNEA_KERNEL_AUTO, RBD_RNEA_KERNEL_BATCH, RBD_RNEA_KERNEL_GROUPS = 0, 1, 2
 RBD_GRAD_KERNEL_AUTO, RBD_GRAD_KERNEL_TREE, RBD_GRAD_KERNEL_COLS, RBD_GRAD_KERNEL_BATCH = 0, 1, 2, 3
 RBD_MINV_PHASE_A_AUTO, RBD_MINV_PHASE_A_LANE, RBD_MINV_PHASE_A_IA8, RBD_MINV_PHASE_A_FUSED = 0, 1, 2, 3
 RBD_OP_RNEA, RBD_OP_RNEA_GRAD, RBD_OP_MINV = 0, 1, 2
+RBD_INTEGRATORS = {"semi_implicit": 0, "euler": 1}      # rbd_rollout (RBD_INTEGRATOR_*)
 
 # every symbol include/rbd_hip.h declares (tests check the built library exports all of them)
 EXPORTED_SYMBOLS = [
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "rbd_ee_pose_f32", "rbd_ee_pose_f64",
     "rbd_second_order_idsva_f32", "rbd_second_order_idsva_f64",
     "rbd_fdsva_so_workspace_bytes", "rbd_fdsva_so_f32", "rbd_fdsva_so_f64",
+    "rbd_rollout_f32", "rbd_rollout_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -126,6 +128,9 @@ def _declare(lib):
         f = getattr(lib, f"rbd_fdsva_so_{sfx}")
         f.restype = c_int
         f.argtypes = [c_void_p, c_void_p, c_void_p, ct, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
+        f = getattr(lib, f"rbd_rollout_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ct, ct, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]
     lib.rbd_fdsva_so_workspace_bytes.restype = c_size_t
     lib.rbd_fdsva_so_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_minv_workspace_bytes.restype = c_size_t

@@ -841,6 +841,63 @@ class RBDReference:
         out = self._ret(out, unb, is_np)
         return out[..., 0, :, :, :], out[..., 1, :, :, :], out[..., 2, :, :, :], out[..., 3, :, :, :]
 
+    # ---- forward-simulation rollouts: rbd_rollout, T steps of aba + integrator in one launch -------------------------
+    def rollout(self, q0, qd0, u, dt, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True):
+        """Integrate ``qdd_t = aba(q_t, qd_t, u_t, GRAVITY)`` over ``T`` steps of size ``dt`` in ONE kernel launch (the
+        state stays on chip between steps) -> ``(q, qd)``.  Not part of the reference: a sampling controller's loop.
+
+        ``integrator``: ``"semi_implicit"`` -- ``qd_{t+1} = qd_t + dt qdd_t``, then ``q_{t+1} = q_t + dt qd_{t+1}`` -- or
+        ``"euler"`` -- ``q_{t+1} = q_t + dt qd_t``, ``qd_{t+1} = qd_t + dt qdd_t``.  No angle wrapping, joint limits,
+        damping or external forces.  Fixed-base robots only.
+
+        Everything with a time axis is TIME-MAJOR.  ``q0, qd0 [B, n]`` with ``u [T, B, n]`` -- or ``[T, n]``, one control
+        sequence shared by every row -- give ``q, qd [T, B, n]``: slice ``t`` is the state after step ``t + 1`` (the
+        initial state is not copied), a contiguous ``[B, n]`` tensor that ``rnea_grad``, ``forward_dynamics_grad`` or
+        ``fdsva_so`` take as it is.  ``trajectory=False`` returns the final state ``[B, n]`` only and writes nothing
+        else.  ``q0 [n]`` with ``u [T, n]`` gives ``[T, n]`` (``[n]``).  numpy in -> float64 numpy out; tensors stay on
+        their device and dtype and run on torch's current stream."""
+        from ._lib import RBD_INTEGRATORS
+        if self.model.floating:
+            raise NotImplementedError("rollout: fixed-base robots only (a floating base needs an integrator on SE(3))")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"rollout: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
+        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"rollout: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        unb = len(sq) == 1
+        B = 1 if unb else sq[0]
+        shared = len(su) == 2
+        if unb and not shared:
+            raise ValueError(f"rollout: q0 [{n}] takes u [T, {n}], got {su}")
+        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
+            raise ValueError(f"rollout: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
+        T = su[0]
+        if T == 0:
+            raise ValueError("rollout: u holds no step (T == 0)")
+        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
+        if isinstance(u, torch.Tensor):
+            if is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            if u.device != dev or u.dtype != dtp:
+                raise TypeError("all inputs must share device and dtype")
+        else:
+            if not is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            u = torch.as_tensor(np.asarray(u, dtype=np.float64), device=dev)
+        u = u.contiguous()
+        with torch.cuda.device(dev):
+            shape = (T, B, n) if trajectory else (B, n)
+            q = torch.empty(shape, device=dev, dtype=dtp)
+            qd = torch.empty(shape, device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_rollout", dtp)(
+                self._ptr(q0), self._ptr(qd0), self._ptr(u), int(shared), float(dt), float(GRAVITY), RBD_INTEGRATORS[integrator],
+                B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), st))
+        if unb:
+            q, qd = q.squeeze(-2), qd.squeeze(-2)
+        return (q.cpu().numpy(), qd.cpu().numpy()) if is_np else (q, qd)
+
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):
         """Site table of a selection, resolved once and cached: ``(chunks of (site_body int32 [k], site_T float64 [k, 12]),

@@ -440,6 +440,9 @@ __attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f64(void);
     return fail(RBD_ERR_UNSUPPORTED, "rbd_fdsva_so: fixed-base robots only (the reference's fdsva_so calls "               \
                 "second_order_idsva_parallel, RBDReference.py:1606-1631)");                                                 \
   }                                                                                                                         \
+  int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) {              \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: fixed-base robots only (a floating base needs an integrator on SE(3))"); \
+  }                                                                                                                         \
   int rbd_aba_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) { return unsupported("rbd_aba"); }                 \
   int rbd_forward_dynamics_grad_##SFX(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, void* ws, \
                                       size_t wsb, void* stream) {                                                           \

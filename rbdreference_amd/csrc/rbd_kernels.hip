@@ -24,7 +24,7 @@
 //   crba, rnea_fpass / rnea_bpass, forward_dynamics(_grad): further rows, same building blocks.
 // The library is built from several translation units of this one file (rbdreference_amd/build.py
 // compiles them in parallel): -DRBD_TU_COMMON, _RNEA_F32, _RNEA_F64, _GRAD_F32, _GRAD_F64,
-// _GRADN_F32, _GRADN_F64 (the qdd = None instantiations of the gradient kernels: half of a gradient unit's compile
+// _ROLL_F32, _ROLL_F64 (rbd_rollout.h), _GRADN_F32, _GRADN_F64 (the qdd = None instantiations of the gradient kernels: half of a gradient unit's compile
 // time), _MINV_F32, _MINV_F64, _FD_F32, _FD_F64, _PASS_F32, _PASS_F64 (each together with -DRBD_TU_SPLIT);
 // without RBD_TU_SPLIT everything is compiled in one unit.
 // -DRBD_FAST_STAGE=1 (first-use family libraries of the gradient, rbdreference_amd/build.py): only the kernel AUTO
@@ -53,6 +53,8 @@
 #define RBD_TU_SO_F64 1
 #define RBD_TU_FDSO_F32 1
 #define RBD_TU_FDSO_F64 1
+#define RBD_TU_ROLL_F32 1
+#define RBD_TU_ROLL_F64 1
 #endif
 
 // Which kernel families this unit needs (everything it does not need is dropped by the preprocessor,
@@ -81,6 +83,9 @@
 #endif
 #if defined(RBD_TU_FDSO_F32) || defined(RBD_TU_FDSO_F64)
 #define RBD_NEED_FDSO 1
+#endif
+#if defined(RBD_TU_ROLL_F32) || defined(RBD_TU_ROLL_F64)
+#define RBD_NEED_ROLL 1
 #endif
 #include "rbd_spatial.h"
 
@@ -2085,6 +2090,9 @@ __global__ __launch_bounds__(64 * MINV_COLS_W, MINV_COLS_MIN_WAVES) void minv_co
 #ifdef RBD_NEED_FDSO
 #include "rbd_fdsva_so.h"
 #endif
+#ifdef RBD_NEED_ROLL
+#include "rbd_rollout.h"
+#endif
 namespace rbdk {
 #ifdef RBD_NO_MINV_LANE
 template <class T>
@@ -2927,6 +2935,41 @@ int fdso_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* ou
 }
 #endif  // RBD_NEED_FDSO
 
+#ifdef RBD_NEED_ROLL
+// rbd_rollout: one launch for all T steps (rbd_rollout.h).  Arguments are checked before the launch.
+template <class T>
+int rollout_launch(const T* q0, const T* qd0, const T* u, int u_shared, T dt, T gravity, int integrator, int64_t B, int64_t steps,
+                   T* q_out, T* qd_out, int trajectory, void* stream) {
+  using namespace rbdk;
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: fixed-base robots only");
+  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rollout: B < 0");
+  if (steps < 0) return fail(RBD_ERR_ARG, "rbd_rollout: T < 0");
+  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "rbd_rollout: dt must be finite");
+  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
+    return fail(RBD_ERR_ARG, "rbd_rollout: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)");
+  if (B == 0 || steps == 0) return 0;
+  if (!q0 || !qd0 || !u || !q_out || !qd_out) return fail(RBD_ERR_ARG, "rbd_rollout: q0, qd0, u, q_out and qd_out must be non-null");
+  if (((reinterpret_cast<uintptr_t>(q_out) | reinterpret_cast<uintptr_t>(qd_out)) & 15u) != 0)
+    return fail(RBD_ERR_ARG, "rbd_rollout: output buffers must be 16-byte aligned");
+  constexpr int lanes = ABA_PARK ? roll_lanes<T>() : 64;
+  const int64_t blocks = (B + lanes - 1) / lanes;
+  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rollout: B too large");
+  // B T n elements of u and of each trajectory: byte offsets stay far inside int64
+  if (steps > (INT64_MAX / 64) / (B * N)) return fail(RBD_ERR_ARG, "rbd_rollout: B * T * n too large");
+  constexpr size_t lds = roll_lds_bytes<T>();
+  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: per-body state does not fit LDS for this robot size");
+  if (int rc = ensure_lds(rollout_kernel<T>, lds)) return rc;
+  const long long row = (long long)B * N;
+  const int aligned = (row * (long long)sizeof(T)) % 16 == 0;      // every trajectory slice starts on a 16-byte boundary
+  hipLaunchKernelGGL(rollout_kernel<T>, dim3((unsigned)blocks, ABA_PARK ? n_groups() : 1), dim3(64), lds, (hipStream_t)stream, q0, qd0,
+                     u, u_shared ? (long long)N : row, u_shared ? 1 : 0, dt, gravity, integrator, (long long)B, (long long)steps,
+                     q_out, qd_out, trajectory ? row : 0LL, aligned);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "rbd_rollout launch");
+  return 0;
+}
+#endif  // RBD_NEED_ROLL
+
 #ifdef RBD_NEED_FD
 template <class T>
 int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, bool want_grad,
@@ -3456,6 +3499,18 @@ int rbd_fdsva_so_f64(const double* q, const double* qd, const double* u, double 
   RbdStreamDevice sd_(stream); return fdso_launch<double>(q, qd, u, gravity, B, out, ws, ws_bytes, stream);
 }
 #endif
+#ifdef RBD_TU_ROLL_F32
+int rbd_rollout_f32(const float* q0, const float* qd0, const float* u, int u_shared, float dt, float gravity, int integrator,
+                    int64_t B, int64_t T, float* q_out, float* qd_out, int trajectory, void* stream) {
+  RbdStreamDevice sd_(stream); return rollout_launch<float>(q0, qd0, u, u_shared, dt, gravity, integrator, B, T, q_out, qd_out, trajectory, stream);
+}
+#endif
+#ifdef RBD_TU_ROLL_F64
+int rbd_rollout_f64(const double* q0, const double* qd0, const double* u, int u_shared, double dt, double gravity,
+                    int integrator, int64_t B, int64_t T, double* q_out, double* qd_out, int trajectory, void* stream) {
+  RbdStreamDevice sd_(stream); return rollout_launch<double>(q0, qd0, u, u_shared, dt, gravity, integrator, B, T, q_out, qd_out, trajectory, stream);
+}
+#endif
 #ifdef RBD_TU_EE_F64
 int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
                     double* pose, double* dpose, void* stream) {
@@ -3502,6 +3557,14 @@ int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const 
   int rbd_second_order_idsva_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) RBD_STUB_BODY("rbd_second_order_idsva")
 #define RBD_STUBS_FDSO(SFX, T)                                                                                                   \
   int rbd_fdsva_so_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_fdsva_so")
+#define RBD_STUBS_ROLL(SFX, T)                                                                                                   \
+  int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) RBD_STUB_BODY("rbd_rollout")
+#ifdef RBD_STUB_ROLL_F32
+RBD_STUBS_ROLL(f32, float)
+#endif
+#ifdef RBD_STUB_ROLL_F64
+RBD_STUBS_ROLL(f64, double)
+#endif
 #ifdef RBD_STUB_FDSO_F32
 RBD_STUBS_FDSO(f32, float)
 #endif
