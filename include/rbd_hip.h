@@ -103,13 +103,20 @@ int rbd_model_info(rbd_model_info_t* out);
  *                          rbd_rnea_grad, phase A of rbd_minv), it decides from this number instead: a shard of
  *                          a sharded batch then runs the kernel the unsharded call would run, so sharded and
  *                          unsharded results are bit-identical row by row (rbdreference_amd.dist.ShardedRBD sets it)
+ *   RBD_OPT_STORE_POLICY   how the one-lane chain gradient kernels (rbd_rnea_grad, rbd_forward_dynamics_grad of a
+ *                          one-chain robot) store their finished rows: AUTO | PLAIN | WRITE_THROUGH (16-byte
+ *                          write-through stores: nothing dirty is left in L2 for the end of the launch to write
+ *                          back) | WRITE_THROUGH_NT (the same, non-temporal).  AUTO goes by the bytes the launch
+ *                          writes: plain up to 4 MiB (a small result stays in L2 for its consumer), write-through
+ *                          up to 64 MiB, non-temporal above.  The same bytes are written either way.
  * rbd_kernel_name writes the name of the kernel (the dominant one of a multi-launch entry point) that
  * `op` would launch for a batch of B rows of elem_size-byte scalars under the current options. */
 #define RBD_OPT_GRAD_KERNEL 0
 #define RBD_OPT_MINV_PHASE_A 1
 #define RBD_OPT_RNEA_KERNEL 2
 #define RBD_OPT_SELECT_BATCH 3
-#define RBD_OPT_COUNT_ 4
+#define RBD_OPT_STORE_POLICY 4
+#define RBD_OPT_COUNT_ 5
 #define RBD_GRAD_KERNEL_AUTO 0
 #define RBD_GRAD_KERNEL_TREE 1
 #define RBD_GRAD_KERNEL_COLS 2
@@ -121,6 +128,10 @@ int rbd_model_info(rbd_model_info_t* out);
 #define RBD_MINV_PHASE_A_LANE 1
 #define RBD_MINV_PHASE_A_IA8 2
 #define RBD_MINV_PHASE_A_FUSED 3
+#define RBD_STORE_POLICY_AUTO 0
+#define RBD_STORE_POLICY_PLAIN 1
+#define RBD_STORE_POLICY_WRITE_THROUGH 2
+#define RBD_STORE_POLICY_WRITE_THROUGH_NT 3
 #define RBD_OP_RNEA 0
 #define RBD_OP_RNEA_GRAD 1
 #define RBD_OP_MINV 2

@@ -24,3 +24,18 @@ struct RbdStreamDevice {
   RbdStreamDevice(const RbdStreamDevice&) = delete;
   RbdStreamDevice& operator=(const RbdStreamDevice&) = delete;
 };
+
+// Store policy of the chain gradient kernels (rbd_spatial.h, store16; RBD_OPT_STORE_POLICY).  Their rows are written once
+// and never read back by the launch.  Left as plain stores they wait, dirty, in L2 -- up to all of it -- for the release at
+// the end of the launch; written through they leave as they are produced.  AUTO goes by the bytes the launch writes
+// (measured on the 7-DoF arm, profiles/store_policy.txt):
+//   <= 4 MiB      plain: the launch gains 0.15 us of 10.8 from writing through, and the result stays in L2 for its consumer
+//   <= 64 MiB     write-through (`sc1`): 1.1 us of 12.6 at 13 MiB, 1.1 us of 20.0 at 52 MiB
+//   above         write-through, non-temporal (`sc1 nt`): 3.4 us of 36.2 at 105 MiB, 3.7 us of 129.8 at 420 MiB, where
+//                 `sc1` alone gains 1.2 and 2.9 (and is the better one at 52 MiB: 18.9 against 19.8 us)
+// Returns the flavour (RBD_STORE_PLAIN / _WT / _WT_NT); `policy` is the option's value.
+constexpr size_t RBD_STORE_WT_MIN_BYTES = (size_t)4 << 20, RBD_STORE_NT_MIN_BYTES = (size_t)64 << 20;
+inline int rbd_store_flavour(int policy, size_t out_bytes) {
+  if (policy != 0) return policy - 1;        // RBD_STORE_POLICY_PLAIN, _WRITE_THROUGH, _WRITE_THROUGH_NT
+  return out_bytes > RBD_STORE_NT_MIN_BYTES ? 2 : out_bytes > RBD_STORE_WT_MIN_BYTES ? 1 : 0;
+}

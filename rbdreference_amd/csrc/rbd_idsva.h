@@ -155,9 +155,11 @@ constexpr int fdc_sym(int i, int j) { return i <= j ? fdc_slot(i, j) : fdc_slot(
 constexpr size_t fdc_ws_scalars(long long B) { return (size_t)((B + 63) / 64) * FDC_NP * 64; }
 template <class T, bool HAS_QDD, bool FDG = false>
 __global__ __launch_bounds__(64, sizeof(T) == 4 ? 2 : 1) void rnea_grad_idsva_kernel(const T* __restrict__ q, const T* __restrict__ qd,
-                                                                const T* __restrict__ qdd, T grav, int use_damping,
+                                                                const T* __restrict__ qdd, T grav, int flags,
                                                                 long long B, T* __restrict__ c_out,
                                                                 T* __restrict__ dcdu, const T* __restrict__ minv_in = nullptr) {
+  const bool use_damping = (flags & RBD_KF_DAMPING) != 0;   // flags: bit 0 damping, bits 1-2 the store flavour (rbd_spatial.h)
+  const int sflav = (flags >> RBD_KF_STORE_SHIFT) & 3;           // wave-uniform: one scalar branch per batch of row stores
   static_assert(!FDG || (grad_max_rows() == N && n_groups() == 1), "fused -Minv epilogue: one-chain robots only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* tile = reinterpret_cast<T*>(smem_raw);
@@ -501,7 +503,7 @@ __global__ __launch_bounds__(64, sizeof(T) == 4 ? 2 : 1) void rnea_grad_idsva_ke
           dq_ij = dot6(t4, Pd[jj]) + dot6(t1, Pdd[jj]);
           dqd_ij = fma_(T(2), dot6(t1, Pd[jj]), dot6(t4, Sv[jj]));
         }
-        if constexpr (jj == j) dqd_ij += sel(use_damping != 0, T(DAMPING[j]), T(0));   // :1336-1341
+        if constexpr (jj == j) dqd_ij += sel(use_damping, T(DAMPING[j]), T(0));   // :1336-1341
         if constexpr (top) {
           my[(j - rs) * GRAD_ROW + jj] = dq_ij;
           my[(j - rs) * GRAD_ROW + N + jj] = dqd_ij;
@@ -658,14 +660,16 @@ __global__ __launch_bounds__(64, sizeof(T) == 4 ? 2 : 1) void rnea_grad_idsva_ke
           if (nv >= 32) {                                  // LDS image == HBM image: flat 16-byte copies
             typedef T V __attribute__((ext_vector_type(VE)));
             const V* src = reinterpret_cast<const V*>(tile);
-            V* dst = reinterpret_cast<V*>(gdst);
             const int g0 = ln;
             constexpr int NV = 32 * RW / VE;
-            sfor<0, (NV + 63) / 64>([&](auto I_) {
-              constexpr int i = decltype(I_)::value;
-              if constexpr ((i + 1) * 64 <= NV) dst[g0 + 64 * i] = src[g0 + 64 * i];
-              else { if (g0 + 64 * i < NV) dst[g0 + 64 * i] = src[g0 + 64 * i]; }
-            });
+            auto put = [&](auto W) {                       // (rbd_spatial.h, store16: the window is this half's rows)
+              sfor<0, (NV + 63) / 64>([&](auto I_) {
+                constexpr int i = decltype(I_)::value;
+                if constexpr ((i + 1) * 64 <= NV) store16(gdst, NV * 16, g0 + 64 * i, src[g0 + 64 * i], decltype(W)::value);
+                else { if (g0 + 64 * i < NV) store16(gdst, NV * 16, g0 + 64 * i, src[g0 + 64 * i], decltype(W)::value); }
+              });
+            };
+            store_dispatch(sflav, put);
             done = true;
           }
         }
@@ -692,10 +696,13 @@ __global__ __launch_bounds__(64, sizeof(T) == 4 ? 2 : 1) void rnea_grad_idsva_ke
           typedef T V __attribute__((ext_vector_type(VE)));
           const int g0 = ln;
           constexpr int NV = CFGS * N / VE;
-          sfor<0, (NV + 63) / 64>([&](auto I_) {
-            constexpr int i = decltype(I_)::value;
-            if (g0 + 64 * i < NV) reinterpret_cast<V*>(cdst)[g0 + 64 * i] = reinterpret_cast<const V*>(tile)[g0 + 64 * i];
-          });
+          auto put = [&](auto W) {
+            sfor<0, (NV + 63) / 64>([&](auto I_) {
+              constexpr int i = decltype(I_)::value;
+              if (g0 + 64 * i < NV) store16(cdst, NV * 16, g0 + 64 * i, reinterpret_cast<const V*>(tile)[g0 + 64 * i], decltype(W)::value);
+            });
+          };
+          store_dispatch(sflav, put);
         } else {
           for (int g = ln; g < nvalid * N; g += 64) cdst[g] = tile[g];
         }

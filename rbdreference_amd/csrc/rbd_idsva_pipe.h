@@ -60,10 +60,14 @@ RBD_DEV void ids_undef(X& x) { asm volatile("" : "=v"(x)); }
 
 template <class T, bool HAS_QDD, bool FDG = false>
 __global__ __launch_bounds__(64, 2) void rnea_grad_idsva_pipe_kernel(const T* __restrict__ q, const T* __restrict__ qd,
-                                                                    const T* __restrict__ qdd, T grav, int use_damping,
+                                                                    const T* __restrict__ qdd, T grav, int flags,
                                                                     long long B, T* __restrict__ c_out,
                                                                     T* __restrict__ dcdu, const T* __restrict__ minv_pk) {
   static_assert(sizeof(T) == 4, "fp32 kernel");
+  // flags: bit 0 damping, bits 1-2 the store flavour (rbd_spatial.h).  The store policy is an argument, wave-uniform, not a
+  // template parameter: one kernel, one name, one scalar branch per batch of stores.
+  const bool use_damping = (flags & RBD_KF_DAMPING) != 0;
+  const int sflav = (flags >> RBD_KF_STORE_SHIFT) & 3;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* tile = reinterpret_cast<T*>(smem_raw);
   const int lane = threadIdx.x;
@@ -389,7 +393,7 @@ __global__ __launch_bounds__(64, 2) void rnea_grad_idsva_pipe_kernel(const T* __
           dq_ij = dot6_acc(t1, Pdd[jj], dot6(t4, Pd[jj]));
           dqd_ij = fma_(T(2), dot6(t1, Pd[jj]), dot6(t4, Sv[jj]));
         }
-        if constexpr (jj == j) dqd_ij += sel(use_damping != 0, T(DAMPING[j]), T(0));   // :1336-1341
+        if constexpr (jj == j) dqd_ij += sel(use_damping, T(DAMPING[j]), T(0));   // :1336-1341
         if constexpr (top) {
           my[(j - rs) * GRAD_ROW + jj] = dq_ij;
           my[(j - rs) * GRAD_ROW + N + jj] = dqd_ij;
@@ -508,12 +512,26 @@ __global__ __launch_bounds__(64, 2) void rnea_grad_idsva_pipe_kernel(const T* __
     });
   };
   auto image_store = [&](int ln, long long cfg0, int h, const V (&buf)[NRD]) {
-    V* dst = reinterpret_cast<V*>(dcdu + (cfg0 + 32 * h) * GRAD_TILE);
-    sfor<0, NRD>([&](auto I_) {
-      constexpr int i = decltype(I_)::value;
-      if constexpr ((i + 1) * 64 <= NV) dst[ln + 64 * i] = buf[i];
-      else { if (ln + 64 * i < NV) dst[ln + 64 * i] = buf[i]; }
-    });
+    T* dst = dcdu + (cfg0 + 32 * h) * GRAD_TILE;           // the window: this half's [32][RW] rows
+    auto put = [&](auto W) {
+      sfor<0, NRD>([&](auto I_) {
+        constexpr int i = decltype(I_)::value;
+        if constexpr ((i + 1) * 64 <= NV) store16(dst, NV * 16, ln + 64 * i, buf[i], decltype(W)::value);
+        else { if (ln + 64 * i < NV) store16(dst, NV * 16, ln + 64 * i, buf[i], decltype(W)::value); }
+      });
+    };
+    store_dispatch(sflav, put);
+  };
+  // the flat [64][n] image of c, pieces already in registers
+  auto c_store = [&](int ln, long long cfg0, const V (&cb)[NRC]) {
+    T* cdst = c_out + cfg0 * N;
+    auto put = [&](auto W) {
+      sfor<0, NRC>([&](auto I_) {
+        constexpr int i = decltype(I_)::value;
+        if (ln + 64 * i < NVC) store16(cdst, NVC * 16, ln + 64 * i, cb[i], decltype(W)::value);
+      });
+    };
+    store_dispatch(sflav, put);
   };
   // the unpipelined flush of one half (ragged tiles, and a block's last tile): as in rnea_grad_idsva_kernel
   auto flush_half_plain = [&](int ln, long long cfg0, int nvalid, int h) {
@@ -537,10 +555,12 @@ __global__ __launch_bounds__(64, 2) void rnea_grad_idsva_pipe_kernel(const T* __
       IDS_WAVE_SYNC();
       T* cdst = c_out + cfg0 * N;
       if (nvalid == CFGS && (CFGS * N) % VE == 0) {
+        V cb[NRC];
         sfor<0, NRC>([&](auto I_) {
           constexpr int i = decltype(I_)::value;
-          if (ln + 64 * i < NVC) reinterpret_cast<V*>(cdst)[ln + 64 * i] = reinterpret_cast<const V*>(tile)[ln + 64 * i];
+          cb[i] = reinterpret_cast<const V*>(tile)[(ln + 64 * i < NVC) ? ln + 64 * i : 0];
         });
+        c_store(ln, cfg0, cb);
       } else {
         for (int g = ln; g < nvalid * N; g += 64) cdst[g] = tile[g];
       }
@@ -617,13 +637,10 @@ __global__ __launch_bounds__(64, 2) void rnea_grad_idsva_pipe_kernel(const T* __
     fwd_body(std::integral_constant<int, 1>{});
     IDS_SB();
     if (!first && c_out != nullptr) {
-      T* cdst = c_out + pcfg0 * N;
       if constexpr (c_flat) {
-        sfor<0, NRC>([&](auto I_) {
-          constexpr int i = decltype(I_)::value;
-          if (ln + 64 * i < NVC) reinterpret_cast<V*>(cdst)[ln + 64 * i] = cbuf[i];
-        });
+        c_store(ln, pcfg0, cbuf);
       } else {
+        T* cdst = c_out + pcfg0 * N;
         for (int g = ln; g < CFGS * N; g += 64) cdst[g] = tile[g];
       }
     }

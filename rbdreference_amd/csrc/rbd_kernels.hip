@@ -2447,7 +2447,14 @@ int rnea_grad_launch1(const T* q, const T* qd, const T* qdd, T gravity, int use_
   return 0;
 }
 
-// One-lane chain kernel (rbd_idsva.h): the grid is what is resident at once, every block walks tiles.
+// flag word of the chain gradient kernels (rbd_idsva.h, rbd_idsva_pipe.h): damping, and the store policy of this launch
+// (rbd_host.h: decided from the bytes the launch writes -- dc_du, and c where it is asked for)
+template <class T>
+inline int chain_kernel_flags(int use_damping, int64_t B, bool with_c) {
+  const size_t out_bytes = (size_t)B * (size_t)(rbdk::GRAD_TILE + (with_c ? rbdk::N : 0)) * sizeof(T);
+  return (use_damping ? rbdk::RBD_KF_DAMPING : 0) |
+         (rbd_store_flavour(rbd_option(RBD_OPT_STORE_POLICY), out_bytes) << rbdk::RBD_KF_STORE_SHIFT);
+}
 template <class T, bool HAS_QDD, bool FDG>
 int idsva_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
                  T* c, T* dc_du, void* stream, const T* minv_in) {
@@ -2458,6 +2465,7 @@ int idsva_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_dampi
   const size_t lds = sizeof(T) * (size_t)64 * IDS_TS;
   if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: output tile does not fit LDS for this robot size");
   int rc, resident = 0;
+  const int kflags = chain_kernel_flags<T>(use_damping, B, c != nullptr);
 #ifndef RBD_EXP_NO_PIPE
   // one chain, fp32, plain rnea_grad: the software-pipelined tile loop (rbd_idsva_pipe.h)
   if constexpr (!FDG && IDS_PIPE_OK && sizeof(T) == 4) {
@@ -2465,7 +2473,7 @@ int idsva_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_dampi
     if ((rc = ensure_lds(kp, lds)) != 0) return rc;
     if ((rc = resident_blocks(kp, 64, lds, &resident)) != 0) return rc;
     const int64_t blocks = tiles < resident ? tiles : resident;
-    hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, use_damping,
+    hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, kflags,
                        (long long)B, c, dc_du, (const T*)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad launch");
@@ -2483,7 +2491,7 @@ int idsva_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_dampi
   resident = resident * RBD_EXP_IDS_GRID_SCALE / 8;   // experiment: k/8 of the resident blocks
 #endif
   const int64_t blocks = tiles < resident ? tiles : resident;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, use_damping,
+  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, kflags,
                      (long long)B, c, dc_du, minv_in);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad launch");
@@ -3004,13 +3012,14 @@ int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd,
     if (e != hipSuccess) return hip_fail(e, "rbd_forward_dynamics_grad (fd_pre_kernel) launch");
     const size_t lds = sizeof(T) * (size_t)64 * IDS_TS;
     int resident = 0;
+    const int kflags = chain_kernel_flags<T>(0, B, false);
 #ifndef RBD_EXP_NO_PIPE
     if constexpr (IDS_PIPE_OK && sizeof(T) == 4) {
       auto kp = rnea_grad_idsva_pipe_kernel<T, true, true>;
       if ((rc = ensure_lds(kp, lds)) != 0) return rc;
       if ((rc = resident_blocks(kp, 64, lds, &resident)) != 0) return rc;
       const int64_t blocks = tiles < resident ? tiles : resident;
-      hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, 0, (long long)B,
+      hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, kflags, (long long)B,
                          (T*)nullptr, dqdd_du, (const T*)Mi);
     } else
 #endif
@@ -3019,7 +3028,7 @@ int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd,
       if ((rc = ensure_lds(k, lds)) != 0) return rc;
       if ((rc = resident_blocks(k, 64, lds, &resident)) != 0) return rc;
       const int64_t blocks = tiles < resident ? tiles : resident;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, 0, (long long)B,
+      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, kflags, (long long)B,
                          (T*)nullptr, dqdd_du, (const T*)Mi);
     }
     e = hipGetLastError();

@@ -42,6 +42,48 @@ RBD_DEV void sfor_down(F&& f) {
 RBD_DEV float launder(float x) { asm volatile("" : "+v"(x)); return x; }
 RBD_DEV double launder(double x) { asm volatile("" : "+v"(x)); return x; }
 
+// One 16-byte global store of piece `piece` (16-byte units) of the wave-uniform window [base, base + bytes), in one of
+// three flavours (RBD_STORE_*):
+//   PLAIN    an ordinary store: the line stays dirty in the XCD's L2 until it is evicted or the release at the end
+//            of the launch writes it back;
+//   WT       write-through (`sc1`): the line goes to memory as it is produced and is dropped from L2;
+//   WT_NT    write-through and non-temporal (`sc1 nt`): the same, and nothing else is displaced on the way.
+// Only whole 16-byte pieces: narrower `sc1` stores are one fabric write each (2.7 - 12x the time per byte), so ragged
+// tails stay plain stores.
+// Form: the raw-buffer builtin.  It is the one way to put `sc1` on a store the COMPILER issues -- its vmcnt
+// bookkeeping, its hazard recogniser (the data registers of a dwordx4 store must not be rewritten by the next
+// instruction) and its scheduler all see the store, which they do not for inline assembly -- and the descriptor bounds
+// the window: a piece outside it would be dropped by the hardware, not written.  (`__builtin_nontemporal_store` gives
+// `nt` alone, which keeps the line in L2.)  `flavour` must fold to a constant where the call is inlined -- the cache
+// policy is an immediate of the instruction -- so callers branch once per batch of stores (store_dispatch).
+constexpr int RBD_STORE_PLAIN = 0, RBD_STORE_WT = 1, RBD_STORE_WT_NT = 2;
+constexpr int RBD_BUF_WORD3 = 0x00020000;              // raw buffer, 32-bit data format (gfx9 descriptor word 3)
+constexpr int RBD_CPOL_SC1 = 16, RBD_CPOL_NT = 2;      // cache-policy bits of the buffer builtins on gfx94x / gfx950
+template <class T, class V>
+RBD_DEV void store16(T* base, int bytes, int piece, V v, int flavour) {
+  static_assert(sizeof(V) == 16, "16-byte pieces only");
+  typedef unsigned U4 __attribute__((ext_vector_type(4)));
+  if (flavour == RBD_STORE_PLAIN) {
+    reinterpret_cast<V*>(base)[piece] = v;
+  } else if (flavour == RBD_STORE_WT) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, v), __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, RBD_BUF_WORD3),
+                                           piece * 16, 0, RBD_CPOL_SC1);
+  } else {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, v), __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, RBD_BUF_WORD3),
+                                           piece * 16, 0, RBD_CPOL_SC1 | RBD_CPOL_NT);
+  }
+}
+// f(std::integral_constant<int, flavour>) under ONE wave-uniform branch
+template <class F>
+RBD_DEV void store_dispatch(int flavour, F&& f) {
+  if (flavour == RBD_STORE_WT) f(std::integral_constant<int, RBD_STORE_WT>{});
+  else if (flavour == RBD_STORE_WT_NT) f(std::integral_constant<int, RBD_STORE_WT_NT>{});
+  else f(std::integral_constant<int, RBD_STORE_PLAIN>{});
+}
+// flag word of the chain gradient kernels (their `int` argument, which carried the damping switch alone: the kernels'
+// symbols stay what they were): bit 0 damping, bits 1-2 the store flavour of the launch
+constexpr int RBD_KF_DAMPING = 1, RBD_KF_STORE_SHIFT = 1;
+
 // by-value select: `c ? x[i] : y[i]` on two lvalues is an lvalue conditional, which clang lowers to a
 // select of ADDRESSES and thereby forces the arrays into scratch memory.
 template <class T>
