@@ -10,42 +10,47 @@
 #include "rbd_fb_world.h"
 #include "rbd_fb_passes.h"
 #include "rbd_fb_minv.h"
-#include "../../include/rbd_hip.h"
 #include "rbd_host.h"
-#include <cstdio>
 #include <cstring>
-#include <atomic>
-#include <cstdint>
 
 static_assert(rbdm::FLOATING_BASE, "rbd_fb_kernels.hip is for floating-base robots");
 
-extern "C" __attribute__((visibility("hidden"))) char* rbd_err_buf(void);
 namespace {
-constexpr size_t RBD_ERR_LEN = 512;
-int fail(int code, const char* msg) { std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s", msg); return code; }
-int hip_fail(hipError_t e, const char* where) {
-  std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: %s", where, hipGetErrorString(e));
-  return (int)e > 0 ? (int)e : 1;
-}
 int unsupported(const char* who) {
-  std::snprintf(rbd_err_buf(), RBD_ERR_LEN,
-                "%s: not available for floating-base robots (the reference's own crba / aba raise for them, "
-                "RBDReference.py:1063, :900)", who);
-  return RBD_ERR_UNSUPPORTED;
+  return fail(RBD_ERR_UNSUPPORTED, "%s: not available for floating-base robots (the reference's own crba / aba raise for them, "
+              "RBDReference.py:1063, :900)", who);
 }
-constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
-extern "C" __attribute__((visibility("hidden"))) std::atomic<int>* rbd_option_slot(int option);
-int rbd_option(int option) { return rbd_option_slot(option)->load(std::memory_order_relaxed); }
-
-// dynamic LDS above 64 KB needs the attribute once per kernel
-template <class K>
-int ensure_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return 0;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return e == hipSuccess ? 0 : hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+// ---- kernel selection: the only readers of the options and the *_ok predicates ------------------------------------------
+// rnea_grad: the world-frame kernel (rbd_fb_world.h) where its identities apply and its LDS plan fits, else the column
+// recursion (rbd_fb.h); RBD_OPT_GRAD_KERNEL = COLS forces the latter.  NONE: 6 > NB, or no LDS plan fits.
+enum class FbGradKind { NONE, WORLD, COLS };
+template <class T>
+FbGradKind grad_fb_select() {
+  if constexpr (!rbdk::grad_fbw_ok<T>()) return rbdk::grad_fb_ok<T>() ? FbGradKind::COLS : FbGradKind::NONE;
+  else if constexpr (!rbdk::grad_fb_ok<T>()) return FbGradKind::WORLD;
+  else return rbd_option(RBD_OPT_GRAD_KERNEL) != RBD_GRAD_KERNEL_COLS ? FbGradKind::WORLD : FbGradKind::COLS;
 }
+// minv: one wave per subtree of the base (rbd_fb_minv.h); RBD_OPT_MINV_PHASE_A = LANE keeps the four-lanes kernel
+enum class FbMinvKind { WAVE, FOUR_LANE };
+template <class T>
+FbMinvKind minv_fb_select() {
+  if constexpr (!rbdk::minv_fbm_ok<T>()) return FbMinvKind::FOUR_LANE;
+  else return rbd_option(RBD_OPT_MINV_PHASE_A) != RBD_MINV_PHASE_A_LANE ? FbMinvKind::WAVE : FbMinvKind::FOUR_LANE;
+}
+// forward dynamics: does the minv kernel compute the bias force from qd itself (no c-only rnea launch)?
+template <class T>
+bool fd_fb_bias_in_minv() {
+#ifdef RBD_FB_EXP_NO_OWN_BIAS      // timing experiment: the c-only rnea launch as before
+  return false;
+#else
+  return minv_fb_select<T>() == FbMinvKind::WAVE;
+#endif
+}
+
+// rnea: one configuration per lane, outputs through LDS images as flat 16-byte stores (rbd_fb_world.h) where they fit
+template <class T>
+constexpr bool rnea_fb_world() { return rbdk::rnea_fbw_lds_bytes<T>() <= LDS_MAX; }
 
 template <class T>
 int rnea_fb_launch(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, T* c, T* v, T* a, T* f, void* stream) {
@@ -55,86 +60,57 @@ int rnea_fb_launch(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, 
   if (!q || !qd || !c) return fail(RBD_ERR_ARG, "rbd_rnea: q, qd and c must be non-null");
   const bool vaf = v || a || f;
   if (vaf && !(v && a && f)) return fail(RBD_ERR_ARG, "rbd_rnea: v, a, f must be all null or all non-null");
-  if (misaligned(c) || misaligned(v) || misaligned(a) || misaligned(f)) return fail(RBD_ERR_ARG, "rbd_rnea: output buffers must be 16-byte aligned");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea: B too large");
+  if (misaligned(c, v, a, f)) return fail(RBD_ERR_ARG, "rbd_rnea: output buffers must be 16-byte aligned");
+  unsigned grid;
+  if (int rc = grid_for(B, 64, "rbd_rnea", &grid)) return rc;
   constexpr size_t lds = rnea_fbw_lds_bytes<T>();
-  if constexpr (lds <= 160 * 1024) {
-    // one configuration per lane, outputs through LDS images as flat 16-byte stores (rbd_fb_world.h)
-    int rc;
-    if (qdd) {
-      auto k = rnea_fbw_kernel<T, true>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-    } else {
-      auto k = rnea_fbw_kernel<T, false>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-    }
-  } else {
-    if (qdd) hipLaunchKernelGGL((rnea_fb_kernel<T, true>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-    else hipLaunchKernelGGL((rnea_fb_kernel<T, false>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_rnea (floating base) launch");
-}
-// which gradient kernel serves this robot: the world-frame kernel (rbd_fb_world.h) where its identities apply and
-// its LDS plan fits, else the column recursion (rbd_fb.h); RBD_OPT_GRAD_KERNEL = COLS forces the latter
-template <class T>
-bool grad_fb_use_world() {
-  if constexpr (!rbdk::grad_fbw_ok<T>()) return false;
-  if constexpr (!rbdk::grad_fb_ok<T>()) return true;
-  return rbd_option(RBD_OPT_GRAD_KERNEL) != RBD_GRAD_KERNEL_COLS;
+  return with_bool(qdd != nullptr, [&](auto HQ) {
+    constexpr bool hq = decltype(HQ)::value;
+    if constexpr (rnea_fb_world<T>())
+      return launch("rbd_rnea (floating base) launch", rnea_fbw_kernel<T, hq>, grid, 64, lds, stream, q, qd, qdd, gravity, B, c, v, a, f);
+    else
+      return launch("rbd_rnea (floating base) launch", rnea_fb_kernel<T, hq>, grid, 64, 0, stream, q, qd, qdd, gravity, B, c, v, a, f);
+  });
 }
 template <class T>
 int grad_fb_launch(const char* who, const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B, T* c, T* v,
                    T* a, T* f, T* dc_du, void* stream) {
   using namespace rbdk;
-  if constexpr (!grad_fb_ok<T>() && !grad_fbw_ok<T>()) {
-    std::snprintf(rbd_err_buf(), RBD_ERR_LEN,
-                  "%s: floating-base rnea_grad needs 6 <= NB (the reference raises IndexError below, RBDReference.py:1168) "
-                  "and an LDS working set that fits; this robot has NB = %d", who, N);
-    return RBD_ERR_UNSUPPORTED;
-  } else {
-    if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B < 0");
-    if (B == 0) return 0;
-    if (!q || !qd || !dc_du) return fail(RBD_ERR_ARG, "rbd_rnea_grad: q, qd and dc_du must be non-null");
-    const bool vaf = v || a || f;
-    if (vaf && !(v && a && f && c)) return fail(RBD_ERR_ARG, "rbd_rnea_with_grad: c, v, a, f must be all non-null");
-    if (misaligned(c) || misaligned(dc_du)) return fail(RBD_ERR_ARG, "rbd_rnea_grad: output buffers must be 16-byte aligned");
-    if (vaf) {   // RBDReference.rnea's outputs: the rnea kernel's own launch
-      int rc = rnea_fb_launch<T>(q, qd, qdd, gravity, B, c, v, a, f, stream);
-      if (rc != 0) return rc;
-    }
-    T* cg = vaf ? nullptr : c;
-    if (grad_fb_use_world<T>()) {
-      if constexpr (grad_fbw_ok<T>()) {
-        const int64_t blocks = (B + 63) / 64;
-        if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-        constexpr size_t lds = fbw_lds_bytes<T>();
-        int rc;
-        if (qdd) {
-          auto k = rnea_grad_fbw_kernel<T, true>;
-          if ((rc = ensure_lds(k, lds)) != 0) return rc;
-          hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * FBW_W), lds, (hipStream_t)stream, q, qd, qdd, gravity, use_damping, (long long)B, cg, dc_du);
-        } else {
-          auto k = rnea_grad_fbw_kernel<T, false>;
-          if ((rc = ensure_lds(k, lds)) != 0) return rc;
-          hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * FBW_W), lds, (hipStream_t)stream, q, qd, qdd, gravity, use_damping, (long long)B, cg, dc_du);
-        }
-      }
-    } else {
-      if constexpr (grad_fb_ok<T>()) {
-        const int64_t blocks = (B + FB_GRAD_C - 1) / FB_GRAD_C;
-        if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-        if (qdd) hipLaunchKernelGGL((rnea_grad_fb_kernel<T, true>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, qdd, gravity, use_damping, (long long)B, cg, dc_du);
-        else hipLaunchKernelGGL((rnea_grad_fb_kernel<T, false>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, qdd, gravity, use_damping, (long long)B, cg, dc_du);
-      }
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "rbd_rnea_grad (floating base) launch");
+  const FbGradKind kind = grad_fb_select<T>();
+  if (kind == FbGradKind::NONE)
+    return fail(RBD_ERR_UNSUPPORTED, "%s: floating-base rnea_grad needs 6 <= NB (the reference raises IndexError below, RBDReference.py:1168) "
+                "and an LDS working set that fits; this robot has NB = %d", who, N);
+  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B < 0");
+  if (B == 0) return 0;
+  if (!q || !qd || !dc_du) return fail(RBD_ERR_ARG, "rbd_rnea_grad: q, qd and dc_du must be non-null");
+  const bool vaf = v || a || f;
+  if (vaf && !(v && a && f && c)) return fail(RBD_ERR_ARG, "rbd_rnea_with_grad: c, v, a, f must be all non-null");
+  if (misaligned(c, dc_du)) return fail(RBD_ERR_ARG, "rbd_rnea_grad: output buffers must be 16-byte aligned");
+  if (vaf) {   // RBDReference.rnea's outputs: the rnea kernel's own launch
+    if (int rc = rnea_fb_launch<T>(q, qd, qdd, gravity, B, c, v, a, f, stream)) return rc;
   }
+  T* cg = vaf ? nullptr : c;
+  unsigned grid;
+  if constexpr (grad_fbw_ok<T>()) {
+    if (kind == FbGradKind::WORLD) {
+      if (int rc = grid_for(B, 64, "rbd_rnea_grad", &grid)) return rc;
+      return with_bool(qdd != nullptr, [&](auto HQ) {
+        return launch("rbd_rnea_grad (floating base) launch", rnea_grad_fbw_kernel<T, decltype(HQ)::value>, grid, 64 * FBW_W, fbw_lds_bytes<T>(),
+                      stream, q, qd, qdd, gravity, use_damping, B, cg, dc_du);
+      });
+    }
+  }
+  if constexpr (grad_fb_ok<T>()) {
+    if (int rc = grid_for(B, FB_GRAD_C, "rbd_rnea_grad", &grid)) return rc;
+    return with_bool(qdd != nullptr, [&](auto HQ) {
+      return launch("rbd_rnea_grad (floating base) launch", rnea_grad_fb_kernel<T, decltype(HQ)::value>, grid, 64, 0, stream,
+                    q, qd, qdd, gravity, use_damping, B, cg, dc_du);
+    });
+  }
+  return 0;
 }
+// with u, c, qdd: qdd = Minv (u - c) leaves the wave kernel's launch (rbd_fb_minv.h; *fused_qdd says so), Minv may then be
+// null; qd instead of c: that kernel computes the bias force itself
 template <class T>
 int minv_fb_launch(const T* q, int64_t B, int dense, T* Minv, void* stream, const T* u = nullptr, const T* cbias = nullptr, T* qdd = nullptr,
                    bool* fused_qdd = nullptr, const T* qd = nullptr, T gravity = T(0)) {
@@ -144,35 +120,27 @@ int minv_fb_launch(const T* q, int64_t B, int dense, T* Minv, void* stream, cons
   if (B == 0) return 0;
   if (!q || (!Minv && !qdd)) return fail(RBD_ERR_ARG, "rbd_minv: q and Minv must be non-null");
   if (misaligned(Minv)) return fail(RBD_ERR_ARG, "rbd_minv: Minv must be 16-byte aligned");
+  unsigned grid;
   if constexpr (minv_fbm_ok<T>()) {
-    // one wave per subtree of the base (rbd_fb_minv.h); RBD_OPT_MINV_PHASE_A = LANE keeps the four-lanes kernel
-    if (rbd_option(RBD_OPT_MINV_PHASE_A) != RBD_MINV_PHASE_A_LANE) {
-      const int64_t nb = (B + 63) / 64;
-      if (nb > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv: B too large");
-      constexpr size_t ldsm = minv_fbm_lds_bytes<T>();
-      auto km = minv_fbm_kernel<T>;
-      int rcm;
-      if ((rcm = ensure_lds(km, ldsm)) != 0) return rcm;
-      // with u, c, qdd: qdd = Minv (u - c) leaves the same launch (rbd_fb_minv.h); Minv may then be null
-      // (qd instead of c: the kernel computes the bias force itself)
-      hipLaunchKernelGGL(km, dim3((unsigned)nb), dim3(64 * FBW_W), ldsm, (hipStream_t)stream, q, (long long)B, dense, Minv, u, cbias, qdd,
-                         cbias ? (const T*)nullptr : qd, gravity);
+    if (minv_fb_select<T>() == FbMinvKind::WAVE) {
+      if (int rc = grid_for(B, 64, "rbd_minv", &grid)) return rc;
       if (fused_qdd) *fused_qdd = qdd != nullptr;
-      hipError_t em = hipGetLastError();
-      return em == hipSuccess ? 0 : hip_fail(em, "rbd_minv (floating base, wave per subtree) launch");
+      return launch("rbd_minv (floating base, wave per subtree) launch", minv_fbm_kernel<T>, grid, 64 * FBW_W, minv_fbm_lds_bytes<T>(), stream,
+                    q, B, dense, Minv, u, cbias, qdd, cbias ? nullptr : qd, gravity);
     }
   }
   if (!Minv) return fail(RBD_ERR_ARG, "rbd_minv: Minv must be non-null");
-  const int64_t blocks = (B + 64 / FB_MINV_L - 1) / (64 / FB_MINV_L);
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv: B too large");
+  if (int rc = grid_for(B, 64 / FB_MINV_L, "rbd_minv", &grid)) return rc;
   constexpr size_t lds = minv_fb_lds_bytes<T>();
-  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_minv: the block's matrices do not fit LDS for this robot size");
-  auto k = minv_fb_kernel<T>;
-  int rc;
-  if ((rc = ensure_lds(k, lds)) != 0) return rc;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, (long long)B, dense, Minv);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_minv (floating base) launch");
+  if (lds > LDS_MAX) return fail(RBD_ERR_UNSUPPORTED, "rbd_minv: the block's matrices do not fit LDS for this robot size");
+  return launch("rbd_minv (floating base) launch", minv_fb_kernel<T>, grid, 64, lds, stream, q, B, dense, Minv);
+}
+// qdd = Minv (u - c) (:1374) where the minv kernel has not done it
+template <class T>
+int fb_apply_launch(const char* who, const T* Mi, const T* u, const T* c, int64_t B, T* qdd, void* stream) {
+  unsigned grid;
+  if (int rc = grid_for(B * rbdk::NV, 256, who, &grid)) return rc;
+  return launch(who, rbdk::fb_apply_kernel<T>, grid, 256, 0, stream, Mi, u, c, B, qdd);
 }
 template <class T>
 int fd_fb_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, void* workspace, size_t wsb, void* stream) {
@@ -192,23 +160,14 @@ int fd_fb_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* q
   // the columns in registers, the matrix itself never written (Minv = nullptr); else rnea, minv into the workspace and
   // the product kernel
   bool fused = false;
-#ifdef RBD_FB_EXP_NO_OWN_BIAS      // timing experiment: the c-only rnea launch as before
-  const bool wave_kernel = false;
-#else
-  const bool wave_kernel = minv_fbm_ok<T>() && rbd_option(RBD_OPT_MINV_PHASE_A) != RBD_MINV_PHASE_A_LANE;
-#endif
-  if (wave_kernel) {
-    if ((rc = minv_fb_launch<T>(q, B, 1, (T*)nullptr, stream, u, (const T*)nullptr, qdd, &fused, qd, gravity)) != 0) return rc;
+  if (fd_fb_bias_in_minv<T>()) {
+    if ((rc = minv_fb_launch<T>(q, B, 1, nullptr, stream, u, nullptr, qdd, &fused, qd, gravity)) != 0) return rc;
     if (fused) return 0;
   }
   if ((rc = rnea_fb_launch<T>(q, qd, nullptr, gravity, B, c, nullptr, nullptr, nullptr, stream)) != 0) return rc;   // :1372
-  if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, (const T*)c, qdd, &fused)) != 0) return rc;
+  if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, c, qdd, &fused)) != 0) return rc;
   if (fused) return 0;
-  const int64_t ab = ((int64_t)B * NV + 255) / 256;
-  if (ab > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_forward_dynamics: B too large");
-  hipLaunchKernelGGL((fb_apply_kernel<T>), dim3((unsigned)ab), dim3(256), 0, (hipStream_t)stream, (const T*)Mi, u, (const T*)c, (long long)B, qdd);   // :1374
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_forward_dynamics (floating base) launch");
+  return fb_apply_launch<T>("rbd_forward_dynamics", Mi, u, c, B, qdd, stream);
 }
 // ---- per-pass surface (README.md:19) ---------------------------------------------------------------------------
 template <class T>
@@ -219,64 +178,49 @@ int rnea_pass_fb_launch(int mode, const T* q, const T* qd, const T* qdd, T gravi
   if (B == 0) return 0;
   if (mode == 1 && (!q || !qd || !v || !a || !f)) return fail(RBD_ERR_ARG, "rbd_rnea_fpass: q, qd, v, a, f must be non-null");
   if (mode == 2 && (!q || !f || !c)) return fail(RBD_ERR_ARG, "rbd_rnea_bpass: q, f, c must be non-null");
-  if (misaligned(c) || misaligned(v) || misaligned(a) || misaligned(f)) return fail(RBD_ERR_ARG, "rbd_rnea pass: output buffers must be 16-byte aligned");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea pass: B too large");
+  if (misaligned(c, v, a, f)) return fail(RBD_ERR_ARG, "rbd_rnea pass: output buffers must be 16-byte aligned");
+  unsigned grid;
+  if (int rc = grid_for(B, 64, "rbd_rnea pass", &grid)) return rc;
   constexpr size_t lds = rnea_fbw_lds_bytes<T>();
-  if constexpr (lds > 160 * 1024) {
-    std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: the [64][6 NB] image does not fit LDS for this robot size", who);
-    return RBD_ERR_UNSUPPORTED;
+  if constexpr (lds > LDS_MAX) {
+    return fail(RBD_ERR_UNSUPPORTED, "%s: the [64][6 NB] image does not fit LDS for this robot size", who);
   } else {
-    int rc;
-    if (mode == 2) {
-      auto k = rnea_fbw_kernel<T, false, 2>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, (const T*)nullptr, (const T*)nullptr, gravity, (long long)B, c, (T*)nullptr, (T*)nullptr, f);
-    } else if (qdd) {
-      auto k = rnea_fbw_kernel<T, true, 1>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, (T*)nullptr, v, a, f);
-    } else {
-      auto k = rnea_fbw_kernel<T, false, 1>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, (long long)B, (T*)nullptr, v, a, f);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, who);
+    if (mode == 2) return launch(who, rnea_fbw_kernel<T, false, 2>, grid, 64, lds, stream, q, nullptr, nullptr, gravity, B, c, nullptr, nullptr, f);
+    return with_bool(qdd != nullptr, [&](auto HQ) {
+      return launch(who, rnea_fbw_kernel<T, decltype(HQ)::value, 1>, grid, 64, lds, stream, q, qd, qdd, gravity, B, nullptr, v, a, f);
+    });
   }
 }
 int grad_pass_needs_six(const char* who) {
-  std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: floating-base gradient passes need NB >= 6 (the reference raises IndexError below, "
-                "RBDReference.py:1168); this robot has NB = %d", who, rbdk::N);
-  return RBD_ERR_UNSUPPORTED;
+  return fail(RBD_ERR_UNSUPPORTED, "%s: floating-base gradient passes need NB >= 6 (the reference raises IndexError below, "
+              "RBDReference.py:1168); this robot has NB = %d", who, rbdk::N);
+}
+// the gradient and minv passes: no LDS, `rows` configurations per block
+template <class... P>
+int pass_fb_launch(const char* who, const char* family, bool args_ok, void (*kernel)(P...), int64_t B, int rows, void* stream,
+                   typename rbd_as_declared<P>::type... args) {
+  if (B < 0) return fail(RBD_ERR_ARG, "%s: B < 0", family);
+  if (B == 0) return 0;
+  if (!args_ok) return fail(RBD_ERR_ARG, "%s: null argument", family);
+  unsigned grid;
+  if (int rc = grid_for(B, rows, family, &grid)) return rc;
+  return launch(who, kernel, grid, 64, 0, stream, args...);
 }
 template <class T, bool ISQD>
 int grad_fpass_fb_launch(const T* q, const T* qd, const T* v, const T* a, T gravity, int64_t B, T* dv, T* da, T* df, void* stream) {
   using namespace rbdk;
   const char* who = ISQD ? "rbd_rnea_grad_fpass_dqd" : "rbd_rnea_grad_fpass_dq";
   if constexpr (N < 6) return grad_pass_needs_six(who);
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad_fpass: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !v || (!ISQD && !a) || !dv || !da || !df) return fail(RBD_ERR_ARG, "rbd_rnea_grad_fpass: null argument");
-  const int64_t blocks = (B + FBP_C - 1) / FBP_C;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad_fpass: B too large");
-  hipLaunchKernelGGL((fb_grad_fpass_kernel<T, ISQD>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, v, a, gravity, (long long)B, dv, da, df);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, who);
+  return pass_fb_launch(who, "rbd_rnea_grad_fpass", q && qd && v && (ISQD || a) && dv && da && df, fb_grad_fpass_kernel<T, ISQD>, B, FBP_C, stream,
+                        q, qd, v, a, gravity, B, dv, da, df);
 }
 template <class T, bool ISQD>
 int grad_bpass_fb_launch(const T* q, const T* f, T* df, int use_damping, int64_t B, T* dc, void* stream) {
   using namespace rbdk;
   const char* who = ISQD ? "rbd_rnea_grad_bpass_dqd" : "rbd_rnea_grad_bpass_dq";
   if constexpr (N < 6) return grad_pass_needs_six(who);
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad_bpass: B < 0");
-  if (B == 0) return 0;
-  if (!q || (!ISQD && !f) || !df || !dc) return fail(RBD_ERR_ARG, "rbd_rnea_grad_bpass: null argument");
-  const int64_t blocks = (B + FBP_C - 1) / FBP_C;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad_bpass: B too large");
-  hipLaunchKernelGGL((fb_grad_bpass_kernel<T, ISQD>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, f, df, use_damping, (long long)B, dc);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, who);
+  return pass_fb_launch(who, "rbd_rnea_grad_bpass", q && (ISQD || f) && df && dc, fb_grad_bpass_kernel<T, ISQD>, B, FBP_C, stream,
+                        q, f, df, use_damping, B, dc);
 }
 template <class T>
 int minv_bpass_fb_launch(const T* q, int64_t B, T* Minv, T* F, T* U, T* Dinv, void* stream) {
@@ -284,26 +228,17 @@ int minv_bpass_fb_launch(const T* q, int64_t B, T* Minv, T* F, T* U, T* Dinv, vo
   if (B < 0) return fail(RBD_ERR_ARG, "rbd_minv_bpass: B < 0");
   if (B == 0) return 0;
   if (!q || !Minv || !F || !U || !Dinv) return fail(RBD_ERR_ARG, "rbd_minv_bpass: null argument");
-  const int64_t blocks = (B + 64 / FB_MINV_L - 1) / (64 / FB_MINV_L);
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv_bpass: B too large");
+  unsigned grid;
+  if (int rc = grid_for(B, 64 / FB_MINV_L, "rbd_minv_bpass", &grid)) return rc;
   hipError_t e = hipMemsetAsync(Minv, 0, (size_t)B * NV * NV * sizeof(T), (hipStream_t)stream);      // entries outside the subtrees stay zero (:700-708)
   if (e == hipSuccess) e = hipMemsetAsync(F, 0, (size_t)B * NV * 6 * NV * sizeof(T), (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "rbd_minv_bpass (clear)");
-  hipLaunchKernelGGL((fb_minv_bpass_kernel<T>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, (long long)B, Minv, F, U, Dinv);
-  e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_minv_bpass (floating base) launch");
+  return launch("rbd_minv_bpass (floating base) launch", fb_minv_bpass_kernel<T>, grid, 64, 0, stream, q, B, Minv, F, U, Dinv);
 }
 template <class T>
 int minv_fpass_fb_launch(const T* q, int64_t B, T* Minv, T* F, const T* U, const T* Dinv, void* stream) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_minv_fpass: B < 0");
-  if (B == 0) return 0;
-  if (!q || !Minv || !F || !U || !Dinv) return fail(RBD_ERR_ARG, "rbd_minv_fpass: null argument");
-  const int64_t blocks = (B + FBP_C - 1) / FBP_C;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv_fpass: B too large");
-  hipLaunchKernelGGL((fb_minv_fpass_kernel<T>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, (long long)B, Minv, F, U, Dinv);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_minv_fpass (floating base) launch");
+  return pass_fb_launch("rbd_minv_fpass (floating base) launch", "rbd_minv_fpass", q && Minv && F && U && Dinv, rbdk::fb_minv_fpass_kernel<T>, B,
+                        rbdk::FBP_C, stream, q, B, Minv, F, U, Dinv);
 }
 // forward_dynamics_grad (:1376-1384): forward dynamics, rnea_grad at that qdd, one batched product.
 // workspace: c [B, NV] | Minv [B, NV, NV] | qdd [B, NV] | dc_du [B, NV, 2 NV]
@@ -320,7 +255,7 @@ int fdg_fb_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* 
   if (B < 0) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: B < 0");
   if (B == 0) return 0;
   if (!q || !qd || !u || !dqdd_du) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: q, qd, u, dqdd_du must be non-null");
-  if (misaligned(dqdd_du) || misaligned(qdd_out)) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: output buffers must be 16-byte aligned");
+  if (misaligned(dqdd_du, qdd_out)) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: output buffers must be 16-byte aligned");
   if (!workspace || wsb < fdg_fb_bytes<T>(B)) return fail(RBD_ERR_WORKSPACE, "rbd_forward_dynamics_grad: workspace missing or smaller than rbd_fd_workspace_bytes()");
   if (misaligned(workspace)) return fail(RBD_ERR_WORKSPACE, "rbd_forward_dynamics_grad: workspace must be 16-byte aligned");
   char* w = reinterpret_cast<char*>(workspace);
@@ -332,58 +267,44 @@ int fdg_fb_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* 
   T* qdd = qdd_out ? qdd_out : qdd_ws;
   int rc;
   bool fused = false;
-#ifdef RBD_FB_EXP_NO_OWN_BIAS
-  const bool wave_kernel = false;
-#else
-  const bool wave_kernel = minv_fbm_ok<T>() && rbd_option(RBD_OPT_MINV_PHASE_A) != RBD_MINV_PHASE_A_LANE;
-#endif
-  if (wave_kernel) {   // :1372-1374 and :1381 in one launch (bias force from qd inside the minv kernel)
-    if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, (const T*)nullptr, qdd, &fused, qd, gravity)) != 0) return rc;
+  if (fd_fb_bias_in_minv<T>()) {   // :1372-1374 and :1381 in one launch (bias force from qd inside the minv kernel)
+    if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, nullptr, qdd, &fused, qd, gravity)) != 0) return rc;
     if (!fused) return fail(RBD_ERR_UNSUPPORTED, "rbd_forward_dynamics_grad: the wave-per-subtree minv kernel did not run");
   } else {
     if ((rc = rnea_fb_launch<T>(q, qd, nullptr, gravity, B, c, nullptr, nullptr, nullptr, stream)) != 0) return rc;   // :1372
-    if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, (const T*)c, qdd, &fused)) != 0) return rc;                   // :1373, :1381 (+ :1374 where fused)
+    if ((rc = minv_fb_launch<T>(q, B, 1, Mi, stream, u, c, qdd, &fused)) != 0) return rc;                             // :1373, :1381 (+ :1374 where fused)
   }
-  if (!fused) {
-    const int64_t ab = ((int64_t)B * NV + 255) / 256;
-    if (ab > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: B too large");
-    hipLaunchKernelGGL((fb_apply_kernel<T>), dim3((unsigned)ab), dim3(256), 0, (hipStream_t)stream, (const T*)Mi, u, (const T*)c, (long long)B, qdd);   // :1374
-  }
-  if ((rc = grad_fb_launch<T>("rbd_forward_dynamics_grad", q, qd, (const T*)qdd, gravity, 0, B, (T*)nullptr, (T*)nullptr, (T*)nullptr, (T*)nullptr, dc, stream)) != 0) return rc;   // :1378
-  constexpr int MMC = negmm_cfgs<T, NV>();
-  const int64_t mb = (B + MMC - 1) / MMC;
-  if (mb > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: B too large");
-  hipLaunchKernelGGL((neg_mm_kernel<T, NV>), dim3((unsigned)mb), dim3(negmm_threads<T, NV>()), 0, (hipStream_t)stream, (const T*)Mi, (const T*)dc, (long long)B, dqdd_du);   // :1382-1383
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_forward_dynamics_grad (floating base) launch");
+  if (!fused && (rc = fb_apply_launch<T>("rbd_forward_dynamics_grad", Mi, u, c, B, qdd, stream)) != 0) return rc;
+  if ((rc = grad_fb_launch<T>("rbd_forward_dynamics_grad", q, qd, qdd, gravity, 0, B, nullptr, nullptr, nullptr, nullptr, dc, stream)) != 0) return rc;   // :1378
+  unsigned grid;
+  if ((rc = grid_for(B, negmm_cfgs<T, NV>(), "rbd_forward_dynamics_grad", &grid)) != 0) return rc;
+  return launch("rbd_forward_dynamics_grad (floating base) launch", neg_mm_kernel<T, NV>, grid, negmm_threads<T, NV>(), 0, stream, Mi, dc, B, dqdd_du);   // :1382-1383
 }
 }  // namespace
 
 extern "C" {
-// kernel names for rbd_kernel_name (COMMON unit)
-__attribute__((visibility("hidden"))) int rbd_grad_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_grad_kernel_name_f64(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_minv_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_minv_kernel_name_f64(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_rnea_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_rnea_kernel_name_f64(int64_t B, char* buf, size_t len);
-
-__attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f32(void);
-__attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f64(void);
+// kernel names for rbd_kernel_name, and rbd_minv_workspace_bytes' question (COMMON unit, rbd_capi.h)
+#define RBD_DECLS_SELECTION(SFX)                                                                           \
+  __attribute__((visibility("hidden"))) int rbd_rnea_kernel_name_##SFX(int64_t B, char* buf, size_t len);  \
+  __attribute__((visibility("hidden"))) int rbd_grad_kernel_name_##SFX(int64_t B, char* buf, size_t len);  \
+  __attribute__((visibility("hidden"))) int rbd_minv_kernel_name_##SFX(int64_t B, char* buf, size_t len);  \
+  __attribute__((visibility("hidden"))) int rbd_minv_needs_ws_##SFX(int64_t B);
+RBD_DECLS_SELECTION(f32)
+RBD_DECLS_SELECTION(f64)
+#undef RBD_DECLS_SELECTION
 
 #define RBD_FB_DEFS(SFX, T)                                                                                                 \
-  int rbd_minv_needs_ws_##SFX(void) { return 0; }                                                                           \
+  int rbd_minv_needs_ws_##SFX(int64_t) { return 0; }                                                                        \
   int rbd_grad_kernel_name_##SFX(int64_t, char* buf, size_t len) {                                                          \
-    std::snprintf(buf, len, "%s<%s,true>", grad_fb_use_world<T>() ? "rnea_grad_fbw_kernel" : "rnea_grad_fb_kernel", sizeof(T) == 4 ? "float" : "double"); \
+    std::snprintf(buf, len, "%s<%s,true>", grad_fb_select<T>() == FbGradKind::WORLD ? "rnea_grad_fbw_kernel" : "rnea_grad_fb_kernel", type_name<T>()); \
     return 0;                                                                                                               \
   }                                                                                                                         \
   int rbd_rnea_kernel_name_##SFX(int64_t, char* buf, size_t len) {                                                          \
-    std::snprintf(buf, len, "%s<%s,true>", rbdk::rnea_fbw_lds_bytes<T>() <= 160 * 1024 ? "rnea_fbw_kernel" : "rnea_fb_kernel", sizeof(T) == 4 ? "float" : "double"); \
+    std::snprintf(buf, len, "%s<%s,true>", rnea_fb_world<T>() ? "rnea_fbw_kernel" : "rnea_fb_kernel", type_name<T>()); \
     return 0;                                                                                                               \
   }                                                                                                                         \
   int rbd_minv_kernel_name_##SFX(int64_t, char* buf, size_t len) {                                                          \
-    const bool m = rbdk::minv_fbm_ok<T>() && rbd_option(RBD_OPT_MINV_PHASE_A) != RBD_MINV_PHASE_A_LANE;                      \
-    std::snprintf(buf, len, "%s<%s>", m ? "minv_fbm_kernel" : "minv_fb_kernel", sizeof(T) == 4 ? "float" : "double");      \
+    std::snprintf(buf, len, "%s<%s>", minv_fb_select<T>() == FbMinvKind::WAVE ? "minv_fbm_kernel" : "minv_fb_kernel", type_name<T>()); \
     return 0;                                                                                                               \
   }                                                                                                                         \
   int rbd_rnea_##SFX(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, T* c, T* v, T* a, T* f, void* stream) {   \

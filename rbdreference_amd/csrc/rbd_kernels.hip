@@ -1,4 +1,6 @@
-// rbd_kernels.hip -- per-robot HIP kernels (gfx950 / CDNA4) + the C-ABI of include/rbd_hip.h.
+// rbd_kernels.hip -- per-robot HIP kernels (gfx950 / CDNA4); the host half behind the C-ABI of include/rbd_hip.h is
+// included at the end: rbd_capi.h (kernel selection, launchers, extern "C" wrappers) over rbd_host.h (errors, options,
+// argument checks, the one launch path) and, in the COMMON unit, rbd_ws_pool.h.
 //
 // Compiled once per robot:  hipcc --offload-arch=gfx950 -include <generated model header> ...
 // (rbdreference_amd/build.py).  The path restated here is RBDReference.rnea / rnea_grad / minv,
@@ -1013,15 +1015,10 @@ __global__ __launch_bounds__(2 * grad_cfgs<T>(), grad_min_waves<T>()) void rnea_
   // rows of the same matrices, so they are given indices 8 apart: the inputs are fetched into ONE L2 instead of
   // `split` (quadruped fp64 B = 65 536: FETCH_SIZE x 2 was 75.8 MB for 18.9 MB of inputs) and partial lines of
   // neighbouring rows meet in the same L2.  Index within the XCD = (configuration block, group), group fastest.
-#ifdef RBD_EXP_NO_XCD_MAP
-  const long long cblk = blockIdx.x / split;
-  const int gsel_x = (int)(blockIdx.x % split);
-#else
   const long long kx = blockIdx.x >> 3;
   const long long cblk = split > 1 ? (kx / split) * 8 + (blockIdx.x & 7) : blockIdx.x;
   const int gsel_x = split > 1 ? (int)(kx % split) : 0;
   if (cblk * CFGS >= B) return;          // (the grid is rounded up to a multiple of 8 configuration blocks; no barrier has been passed)
-#endif
   const long long cfg0 = cblk * CFGS;
   const long long rem = B - cfg0;
   const int nvalid = rem < CFGS ? (int)rem : CFGS;
@@ -2107,1527 +2104,6 @@ constexpr bool minv_use_lane() { return minv_lane_ok<T>(); }
 constexpr size_t MINV_WS_PER_CFG = (minv_use_lane<float>() && minv_use_lane<double>()) ? 0 : (size_t)N * MINV_WS;
 }  // namespace rbdk
 
-// =============================================================================================
-// C-ABI (include/rbd_hip.h)
-// =============================================================================================
-#include "../../include/rbd_hip.h"
-#include "rbd_host.h"
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <unordered_map>
-#include <vector>
-constexpr int RBD_MAX_DEVICES = 16;
-
-
-// thread-local message buffer behind rbd_last_error(); one instance, owned by the COMMON unit
-extern "C" __attribute__((visibility("hidden"))) char* rbd_err_buf(void);
-#ifdef RBD_TU_COMMON
-extern "C" char* rbd_err_buf(void) {
-  static thread_local char buf[512] = "";
-  return buf;
-}
-#endif
-constexpr size_t RBD_ERR_LEN = 512;
-
-// Tuning options (rbd_set_option): one instance, owned by the COMMON unit; relaxed atomics -- an option
-// only ever selects between kernels that compute the same result.
-extern "C" __attribute__((visibility("hidden"))) std::atomic<int>* rbd_option_slot(int option);
-#ifdef RBD_TU_COMMON
-extern "C" std::atomic<int>* rbd_option_slot(int option) {
-  static std::atomic<int> slots[RBD_OPT_COUNT_];
-  return option >= 0 && option < RBD_OPT_COUNT_ ? &slots[option] : nullptr;
-}
-#endif
-static inline int rbd_option(int option) { return rbd_option_slot(option)->load(std::memory_order_relaxed); }
-// the batch size kernel selection looks at: the call's own, unless the caller has declared the global batch it is a shard of
-static inline int64_t rbd_select_batch(int64_t B) {
-  const int g = rbd_option(RBD_OPT_SELECT_BATCH);
-  return g > 0 ? (int64_t)g : B;
-}
-
-// The forward-dynamics units reuse the kernels of the RNEA / MINV / GRAD units through these entry
-// points instead of instantiating the same templates a second time (Atlas: the fp64 gradient kernel
-// alone costs 200 s of compile time).  rbd_minv_fd_* = rbd_minv_* plus the fused qdd = Minv (u - c).
-extern "C" {
-// qdd = None gradient launches (GRADN units) for the GRAD / FD units
-__attribute__((visibility("hidden"))) int rbd_grad_noqdd_f32(const float* q, const float* qd, float gravity, int use_damping, int64_t B, float* c, float* dc_du, void* stream);
-__attribute__((visibility("hidden"))) int rbd_grad_noqdd_f64(const double* q, const double* qd, double gravity, int use_damping, int64_t B, double* c, double* dc_du, void* stream);
-__attribute__((visibility("hidden"))) int rbd_grad_cols_noqdd_f32(const float* q, const float* qd, float gravity, int use_damping, int64_t B, float* c, float* v, float* a, float* f, float* dc_du, void* stream);
-__attribute__((visibility("hidden"))) int rbd_grad_cols_noqdd_f64(const double* q, const double* qd, double gravity, int use_damping, int64_t B, double* c, double* v, double* a, double* f, double* dc_du, void* stream);
-__attribute__((visibility("hidden"))) int rbd_minv_fd_f32(const float* q, int64_t B, float* Minv, void* workspace, size_t wsb,
-                                                          void* stream, const float* u, const float* c, float* qdd, const float* qd, float gravity);
-__attribute__((visibility("hidden"))) int rbd_minv_fd_f64(const double* q, int64_t B, double* Minv, void* workspace, size_t wsb,
-                                                          void* stream, const double* u, const double* c, double* qdd, const double* qd, double gravity);
-}
-
-namespace {
-int fail(int code, const char* msg) {
-  std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s", msg);
-  return code;
-}
-int hip_fail(hipError_t e, const char* where) {
-  std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: %s", where, hipGetErrorString(e));
-  return (int)e > 0 ? (int)e : 1;
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is needed once per kernel (and device), not per
-// launch: the granted sizes are remembered.
-template <class K>
-int ensure_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return 0;
-  static std::mutex mu;
-  static std::unordered_map<const void*, size_t> granted[RBD_MAX_DEVICES];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void* key = reinterpret_cast<const void*>(kernel);
-  const int slot = dev >= 0 && dev < RBD_MAX_DEVICES ? dev : 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = granted[slot].find(key);
-    if (it != granted[slot].end() && it->second >= bytes) return 0;
-  }
-  hipError_t e = hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-  std::lock_guard<std::mutex> g(mu);
-  granted[slot][key] = bytes;
-  return 0;
-}
-
-// Blocks of `threads` threads and `lds` bytes that are resident at once on the current device
-// (occupancy per CU x CUs), remembered per kernel and device: the grid of the tile-walking kernels.
-template <class K>
-int resident_blocks(K kernel, int threads, size_t lds, int* out) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, int> known[RBD_MAX_DEVICES];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const void* key = reinterpret_cast<const void*>(kernel);
-  const int slot = dev >= 0 && dev < RBD_MAX_DEVICES ? dev : 0;
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = known[slot].find(key);
-    if (it != known[slot].end()) { *out = it->second; return 0; }
-  }
-  int per_cu = 0, cus = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
-  if (e != hipSuccess) return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor");
-  e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return hip_fail(e, "hipDeviceGetAttribute(MultiprocessorCount)");
-  const int n = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  std::lock_guard<std::mutex> g(mu);
-  known[slot][key] = n;
-  *out = n;
-  return 0;
-}
-}  // namespace
-
-// Library-owned scratch of the workspace gradient kernel (rbd_idsva_tree_ws.h): one buffer per (device, stream), keyed
-// by the STREAM's device (hipStreamGetDevice; the null stream belongs to the calling thread's current device).
-// Launches on one stream are ordered and share it; launches on different streams get different buffers.
-// Lifetime rule: a buffer that was ever handed out is NEVER freed or moved by a later call -- launches in flight, bound
-// launches and captured hipGraphs may hold its address.  The callers ask for a size that depends on the kernel's
-// occupancy, not on B, so a (device, stream) normally sees one allocation; should a later call need more (another
-// kernel of the library), a larger buffer is allocated NEXT TO the old one, which is retired, not released.  Only
-// rbd_release_workspaces() frees (after hipDeviceSynchronize, by contract with no call of this library in flight and
-// no graph that contains one still alive).  The first call on a stream allocates (hipMalloc is not capturable: run a
-// call once before capturing it into a graph, as for every kernel that needs hipFuncSetAttribute); no call ever
-// synchronises the device.  One pool, owned by the COMMON unit.
-extern "C" __attribute__((visibility("hidden"))) int rbd_stream_workspace(void* stream, size_t bytes, void** out);
-#ifdef RBD_TU_COMMON
-namespace {
-struct RbdWsBuf { void* p = nullptr; size_t n = 0; };
-struct RbdWsEntry { RbdWsBuf cur; std::vector<RbdWsBuf> retired; };
-std::mutex& rbd_ws_mutex() { static std::mutex mu; return mu; }
-std::unordered_map<const void*, RbdWsEntry>* rbd_ws_pool() {
-  static std::unordered_map<const void*, RbdWsEntry> pool[RBD_MAX_DEVICES];
-  return pool;
-}
-int rbd_ws_device_of(void* stream, int* dev) {
-  int d = 0;
-  hipError_t e = stream ? hipStreamGetDevice((hipStream_t)stream, &d) : hipGetDevice(&d);
-  if (e != hipSuccess) { (void)hipGetLastError(); e = hipGetDevice(&d); }
-  if (e != hipSuccess) return (int)e;
-  *dev = d;
-  return 0;
-}
-}  // namespace
-extern "C" int rbd_stream_workspace(void* stream, size_t bytes, void** out) {
-  int dev = 0;
-  if (rbd_ws_device_of(stream, &dev) != 0) return hip_fail(hipErrorInvalidDevice, "rbd workspace: device of the stream");
-  if (dev < 0 || dev >= RBD_MAX_DEVICES) return fail(RBD_ERR_UNSUPPORTED, "rbd workspace: device index beyond RBD_MAX_DEVICES");
-  std::lock_guard<std::mutex> g(rbd_ws_mutex());
-  RbdWsEntry& en = rbd_ws_pool()[dev][stream];
-  if (en.cur.n < bytes) {
-    int cur_dev = dev;
-    (void)hipGetDevice(&cur_dev);
-    if (cur_dev != dev) (void)hipSetDevice(dev);            // allocate on the stream's device
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (cur_dev != dev) (void)hipSetDevice(cur_dev);
-    if (e != hipSuccess) return hip_fail(e, "rbd workspace hipMalloc");
-    if (en.cur.p) en.retired.push_back(en.cur);               // may still be referenced: kept, not freed
-    en.cur.p = p;
-    en.cur.n = bytes;
-  }
-  *out = en.cur.p;
-  return 0;
-}
-extern "C" int rbd_release_workspaces(void) {
-  std::lock_guard<std::mutex> g(rbd_ws_mutex());
-  int cur_dev = 0;
-  const bool have_dev = hipGetDevice(&cur_dev) == hipSuccess;
-  if (!have_dev) (void)hipGetLastError();
-  int rc = 0;
-  for (int dev = 0; dev < RBD_MAX_DEVICES; ++dev) {
-    auto& m = rbd_ws_pool()[dev];
-    if (m.empty()) continue;
-    hipError_t e = hipSetDevice(dev);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess && rc == 0) rc = hip_fail(e, "rbd_release_workspaces: hipDeviceSynchronize");
-    for (auto& kv : m) {
-      if (kv.second.cur.p) (void)hipFree(kv.second.cur.p);
-      for (auto& b : kv.second.retired) (void)hipFree(b.p);
-    }
-    m.clear();
-  }
-  if (have_dev) (void)hipSetDevice(cur_dev);
-  return rc;
-}
-#endif
-
-namespace {
-
-#ifdef RBD_NEED_RNEA
-template <class T>
-int rnea_launch(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, T* c, T* v, T* a, T* f,
-                void* stream, int fpass_only = 0) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || (!c && !fpass_only)) return fail(RBD_ERR_ARG, "rbd_rnea: q, qd and c must be non-null");
-  if (fpass_only && !(v && a && f)) return fail(RBD_ERR_ARG, "rbd_rnea_fpass: v, a, f must be non-null");
-  const bool vaf = v || a || f;
-  if (vaf && !(v && a && f)) return fail(RBD_ERR_ARG, "rbd_rnea: v, a, f must be all null or all non-null");
-  if (((reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(f)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_rnea: output buffers must be 16-byte aligned");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea: B too large");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = rnea_lds_bytes<T>(true);
-  const size_t lds_c = rnea_lds_bytes<T>(false);
-  int rc;
-  if constexpr (rnea_segs_ok<T>()) {
-    // one wave per segment (stem / limb / limb-less group): Atlas fp32 B = 16 384
-    const int ropt = rbd_option(RBD_OPT_RNEA_KERNEL);
-    if (vaf && !fpass_only && ropt != RBD_RNEA_KERNEL_BATCH && ropt != RBD_RNEA_KERNEL_GROUPS) {
-      constexpr size_t ldss = rnea_segs_lds<T>();
-      if (qdd) {
-        auto k = rnea_segments_kernel<T, true>;
-        if ((rc = ensure_lds(k, ldss)) != 0) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * RS_WAVES), ldss, s, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-      } else {
-        auto k = rnea_segments_kernel<T, false>;
-        if ((rc = ensure_lds(k, ldss)) != 0) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * RS_WAVES), ldss, s, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-      }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "rbd_rnea (segment waves) launch");
-      return 0;
-    }
-  }
-  if constexpr (rnea_groups_ok<T>() && !(RBD_FAST_STAGE && rnea_segs_ok<T>())) {   // (first-use build: not next to the segment kernel AUTO picks)
-    // one wave per independent root group: faster than one lane per configuration at every batch size
-    // measured (Atlas fp32: 17.4 -> 13.5 us at B = 16 384, 235 -> 167 us at B = 262 144; quadruped fp32
-    // B = 1M: 199 -> 174 us = 6.4 TB/s)
-    const int ropt = rbd_option(RBD_OPT_RNEA_KERNEL);
-    if (vaf && !fpass_only && ropt != RBD_RNEA_KERNEL_BATCH) {
-      const size_t ldsg = 2 * sizeof(T) * 64 * (size_t)odd_pad<6 * N>();
-      if (qdd) {
-        auto k = rnea_groups_kernel<T, true>;
-        if ((rc = ensure_lds(k, ldsg)) != 0) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * RG_WAVES), ldsg, s, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-      } else {
-        auto k = rnea_groups_kernel<T, false>;
-        if ((rc = ensure_lds(k, ldsg)) != 0) return rc;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * RG_WAVES), ldsg, s, q, qd, qdd, gravity, (long long)B, c, v, a, f);
-      }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "rbd_rnea (group waves) launch");
-      return 0;
-    }
-  }
-#define RBD_LAUNCH_RNEA(HQ, VAF, LDS)                                                              \
-  do {                                                                                             \
-    auto k = rnea_kernel<T, HQ, VAF>;                                                              \
-    if ((rc = ensure_lds(k, LDS)) != 0) return rc;                                                 \
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), LDS, s, q, qd, qdd, gravity,           \
-                       (long long)B, c, v, a, f, fpass_only);                                      \
-  } while (0)
-  if (qdd) { if (vaf) RBD_LAUNCH_RNEA(true, true, lds); else RBD_LAUNCH_RNEA(true, false, lds_c); }
-  else     { if (vaf) RBD_LAUNCH_RNEA(false, true, lds); else RBD_LAUNCH_RNEA(false, false, lds_c); }
-#undef RBD_LAUNCH_RNEA
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_rnea launch");
-  return 0;
-}
-
-template <class T>
-int rnea_bpass_launch(const T* q, T* f, int64_t B, T* c, void* stream) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_bpass: B < 0");
-  if (B == 0) return 0;
-  if (!q || !f || !c) return fail(RBD_ERR_ARG, "rbd_rnea_bpass: q, f and c must be non-null");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_bpass: B too large");
-  const size_t lds = sizeof(T) * 64 * (size_t)odd_pad<6 * N>();
-  auto k = rnea_bpass_kernel<T>;
-  int rc;
-  if ((rc = ensure_lds(k, lds)) != 0) return rc;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, f, (long long)B, c);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_rnea_bpass launch");
-  return 0;
-}
-
-// the kernel rbd_rnea launches when v, a, f are requested (c alone is always the one-lane kernel)
-template <class T>
-int rnea_kernel_name(int64_t, char* buf, size_t len) {
-  using namespace rbdk;
-  const char* t = sizeof(T) == 4 ? "float" : "double";
-  const int ropt = rbd_option(RBD_OPT_RNEA_KERNEL);
-  bool done = false;
-  if constexpr (rnea_segs_ok<T>()) {
-    if (!done && ropt != RBD_RNEA_KERNEL_BATCH && ropt != RBD_RNEA_KERNEL_GROUPS) { std::snprintf(buf, len, "rnea_segments_kernel<%s>", t); done = true; }
-  }
-  if constexpr (rnea_groups_ok<T>()) {
-    if (!done && ropt != RBD_RNEA_KERNEL_BATCH) { std::snprintf(buf, len, "rnea_groups_kernel<%s>", t); done = true; }
-  }
-  if (!done) std::snprintf(buf, len, "rnea_kernel<%s>", t);
-  return 0;
-}
-
-#endif  // RBD_NEED_RNEA
-
-#ifdef RBD_NEED_GRAD
-// launches exactly one instantiation (the FD translation units use this to avoid compiling the
-// variants they never call)
-template <class T, bool HAS_QDD, bool FDG>
-int rnea_grad_launch1(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                      T* c, T* dc_du, void* stream, const T* minv_in) {
-  using namespace rbdk;
-  constexpr int CFGS = grad_cfgs<T>();
-  const int64_t blocks = (B + CFGS - 1) / CFGS;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-  if ((reinterpret_cast<uintptr_t>(dc_du) & 15u) != 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad: dc_du must be 16-byte aligned");
-  // (with one block per group the Minv tile holds that group's rows only: 55 -> 28 KB for the quadruped in fp64, i.e. five
-  // 64-thread blocks per CU instead of two)
-  constexpr bool SPLIT = GRAD_PER_ROOT && n_groups() > 1;
-  const size_t lds = sizeof(T) * ((size_t)CFGS * GRAD_TS + (FDG ? (size_t)CFGS * (SPLIT ? (size_t)((grad_max_rows() * N) | 1) : (size_t)(N * N)) : 0));
-  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: output tile does not fit LDS for this robot size");
-  auto k = rnea_grad_kernel<T, HAS_QDD, FDG>;
-  int rc;
-  if ((rc = ensure_lds(k, lds)) != 0) return rc;
-  // independent root subtrees get their own blocks -- also with the fused -Minv epilogue (round 4): Minv and dc_du are
-  // block-diagonal over the groups, so a group's block stages that group's Minv rows only (the quadruped's fp64
-  // forward_dynamics_grad gradient leg: 151 us with every leg in one block, serial)
-  const int split = (GRAD_PER_ROOT && n_groups() > 1) ? n_groups() : 1;
-#ifdef RBD_EXP_NO_XCD_MAP
-  const int64_t grid = blocks * split;
-#else
-  const int64_t grid = split > 1 ? ((blocks + 7) / 8 * 8) * split : blocks;     // whole XCD rounds (the kernel's block -> (configurations, group) map)
-#endif
-  if (grid > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(2 * CFGS), lds, (hipStream_t)stream, q, qd, qdd, gravity,
-                     use_damping, (long long)B, c, dc_du, minv_in, split);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad launch");
-  return 0;
-}
-
-// flag word of the chain gradient kernels (rbd_idsva.h, rbd_idsva_pipe.h): damping, and the store policy of this launch
-// (rbd_host.h: decided from the bytes the launch writes -- dc_du, and c where it is asked for)
-template <class T>
-inline int chain_kernel_flags(int use_damping, int64_t B, bool with_c) {
-  const size_t out_bytes = (size_t)B * (size_t)(rbdk::GRAD_TILE + (with_c ? rbdk::N : 0)) * sizeof(T);
-  return (use_damping ? rbdk::RBD_KF_DAMPING : 0) |
-         (rbd_store_flavour(rbd_option(RBD_OPT_STORE_POLICY), out_bytes) << rbdk::RBD_KF_STORE_SHIFT);
-}
-template <class T, bool HAS_QDD, bool FDG>
-int idsva_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                 T* c, T* dc_du, void* stream, const T* minv_in) {
-  using namespace rbdk;
-  const int64_t tiles = (B + 63) / 64;
-  if (tiles > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-  if ((reinterpret_cast<uintptr_t>(dc_du) & 15u) != 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad: dc_du must be 16-byte aligned");
-  const size_t lds = sizeof(T) * (size_t)64 * IDS_TS;
-  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: output tile does not fit LDS for this robot size");
-  int rc, resident = 0;
-  const int kflags = chain_kernel_flags<T>(use_damping, B, c != nullptr);
-#ifndef RBD_EXP_NO_PIPE
-  // one chain, fp32, plain rnea_grad: the software-pipelined tile loop (rbd_idsva_pipe.h)
-  if constexpr (!FDG && IDS_PIPE_OK && sizeof(T) == 4) {
-    auto kp = rnea_grad_idsva_pipe_kernel<T, HAS_QDD>;
-    if ((rc = ensure_lds(kp, lds)) != 0) return rc;
-    if ((rc = resident_blocks(kp, 64, lds, &resident)) != 0) return rc;
-    const int64_t blocks = tiles < resident ? tiles : resident;
-    hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, kflags,
-                       (long long)B, c, dc_du, (const T*)nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad launch");
-    return 0;
-  } else
-#endif
-  {   // (an else branch: the kernel below is not even instantiated where the pipelined one serves the robot)
-  auto k = rnea_grad_idsva_kernel<T, HAS_QDD, FDG>;
-  if ((rc = ensure_lds(k, lds)) != 0) return rc;
-  if ((rc = resident_blocks(k, 64, lds, &resident)) != 0) return rc;
-#ifdef RBD_EXP_IDS_GRID_TILES
-  resident = 0x7fffffff;                   // experiment: one block per tile (no tile walking)
-#endif
-#ifdef RBD_EXP_IDS_GRID_SCALE
-  resident = resident * RBD_EXP_IDS_GRID_SCALE / 8;   // experiment: k/8 of the resident blocks
-#endif
-  const int64_t blocks = tiles < resident ? tiles : resident;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, qdd, gravity, kflags,
-                     (long long)B, c, dc_du, minv_in);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad launch");
-  return 0;
-  }
-}
-
-// Small batches: one lane per (configuration, derivative column) (rbd_grad_cols.h).  Chosen when the
-// batch-parallel kernels would leave most of the chip idle: at most two of its waves per SIMD.
-constexpr int64_t GRAD_COLS_MAX_WAVES = 2048;
-template <class T>
-inline bool grad_use_cols(int64_t B) {
-  using namespace rbdk;
-  if (RBD_FAST_STAGE || !grad_cols_ok<T>()) return false;
-  const int opt = rbd_option(RBD_OPT_GRAD_KERNEL);
-  if (opt == RBD_GRAD_KERNEL_COLS) return true;
-  if (opt != RBD_GRAD_KERNEL_AUTO) return false;
-  return (rbd_select_batch(B) + GC_CPW - 1) / GC_CPW <= GRAD_COLS_MAX_WAVES;
-}
-template <class T, bool HAS_QDD>
-int grad_cols_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                     T* c, T* v, T* a, T* f, T* dc_du, void* stream) {
-  using namespace rbdk;
-  if constexpr (RBD_FAST_STAGE || !grad_cols_ok<T>()) {
-    return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: the column kernel is not built for this robot size");
-  } else {
-    const int64_t blocks = (B + GC_CPW - 1) / GC_CPW;
-    if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-    hipLaunchKernelGGL((rnea_grad_cols_kernel<T, HAS_QDD>), dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, q, qd, qdd,
-                       gravity, use_damping, (long long)B, c, v, a, f, dc_du);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad (column kernel) launch");
-    return 0;
-  }
-}
-
-// fp64 trees on the workspace kernel (rbd_idsva_tree_ws.h).  Default where the fp32 default is the tree kernel
-// (Atlas: the two-lane column kernel spilled 388 registers there and is no longer built in fp64); with
-// RBD_OPT_GRAD_KERNEL = TREE for every other fp64 robot whose root path does not fit the register plan.
-#ifndef RBD_HAVE_TWS
-template <class T>
-constexpr bool tws_built() { return false; }
-template <class T>
-constexpr bool tws_only() { return false; }
-template <class T, bool HAS_QDD>
-int tree_ws_launch(const T*, const T*, const T*, T, int, int64_t, T*, T*, void*) {
-  return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: the workspace tree kernel is not part of this unit");
-}
-#else
-template <class T>
-constexpr bool tws_built() {
-  using namespace rbdk;
-#ifdef RBD_TWS_FORCE                                          // experiments: the workspace kernel for every eligible robot
-  return tws_ok<T>();
-#else
-  constexpr bool reg_plan = N <= 12 && rbdm::MAXDEPTH <= 5;   // served by rnea_grad_tree_kernel<double>
-  if constexpr (!tws_ok<T>() || reg_plan) return false;
-  else return GRAD_TREE_DEFAULT || !RBD_FAST_STAGE;
-#endif
-}
-template <class T>
-#ifdef RBD_TWS_FORCE
-constexpr bool tws_only() { return tws_built<T>(); }
-#else
-constexpr bool tws_only() { return tws_built<T>() && rbdk::GRAD_TREE_DEFAULT; }
-#endif
-template <class T, bool HAS_QDD>
-int tree_ws_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B, T* c, T* dc_du, void* stream) {
-  using namespace rbdk;
-  if constexpr (!tws_built<T>()) {
-    return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: the workspace tree kernel is not built for this robot");
-  } else {
-    constexpr size_t lds = tws_lds_bytes<T>();
-    auto k = rnea_grad_tree_ws_kernel<T, HAS_QDD>;
-    int rc, resident = 0;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    if ((rc = resident_blocks(k, 64 * TWS_W, lds, &resident)) != 0) return rc;
-    const int yroots = TWS_MULTI ? 1 : tree_n_roots();
-    // one launch covers what is resident at once; larger batches walk the same workspace chunk by chunk
-    int64_t xblocks = resident / yroots;
-    if (xblocks < 1) xblocks = 1;
-    const int64_t need = (B + 63) / 64;
-    if (xblocks > need) xblocks = need;
-    const int64_t rows = xblocks * 64;
-    // sized by what is resident at once (never by B), one region per (x, root) block of the single-wave layout: a
-    // (device, stream) sees ONE allocation for this kernel, whatever batch sizes follow (rbd_stream_workspace)
-    const int64_t xres = resident / yroots > 0 ? resident / yroots : 1;
-    void* ws = nullptr;
-    if ((rc = rbd_stream_workspace(stream, (size_t)xres * 64 * yroots * TWS_SLOTS * sizeof(T), &ws)) != 0) return rc;
-    T* pws = reinterpret_cast<T*>(ws);
-    T* ews = pws + (size_t)64 * TWS_PATH_SLOTS;   // [block][slot][lane]: a block's entry slots follow its path slots
-    for (int64_t r0 = 0; r0 < B; r0 += rows) {
-      const int64_t nb = B - r0 < rows ? B - r0 : rows;
-      hipLaunchKernelGGL(k, dim3((unsigned)((nb + 63) / 64), yroots), dim3(64 * TWS_W), lds, (hipStream_t)stream, q + r0 * N, qd + r0 * N,
-                         qdd ? qdd + r0 * N : nullptr, gravity, use_damping, (long long)nb, c ? c + r0 * N : nullptr,
-                         dc_du + r0 * (2 * N * N), pws, ews);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad (workspace tree kernel) launch");
-    }
-    return 0;
-  }
-}
-#endif  // RBD_HAVE_TWS
-
-// One instantiation per (T, HAS_QDD): the forward-dynamics units only ever need HAS_QDD = true.
-template <class T, bool HAS_QDD>
-int rnea_grad_launch_q(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                       T* c, T* dc_du, void* stream) {
-  using namespace rbdk;
-  if (grad_use_cols<T>(B)) return grad_cols_launch<T, HAS_QDD>(q, qd, qdd, gravity, use_damping, B, c, nullptr, nullptr, nullptr, dc_du, stream);
-  // fp32 robots whose default is the tree kernel never build the column kernel (Atlas: 404 VGPRs of
-  // code nobody runs); fp64 x big tree would need > 512 VGPRs and is not built either.
-  if constexpr (tws_built<T>()) {
-    if (tws_only<T>() || rbd_option(RBD_OPT_GRAD_KERNEL) == RBD_GRAD_KERNEL_TREE)
-      return tree_ws_launch<T, HAS_QDD>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream);
-  }
-  constexpr bool TREE_ONLY = GRAD_TREE_DEFAULT && sizeof(T) == 4;
-  constexpr bool TREE_BUILT = RBD_FAST_STAGE ? TREE_ONLY : GRAD_TREE_OK && (sizeof(T) == 4 || (N <= 12 && rbdm::MAXDEPTH <= 5));   // fp64: the root path's S / psid / psidd (36 registers per body) must fit 512 VGPRs without scratch
-  if constexpr (TREE_BUILT) {
-    constexpr size_t lds = tree_lds_bytes<T>();
-    static_assert(!TREE_ONLY || lds <= 160 * 1024, "tree kernel is the only gradient kernel of this robot but does not fit LDS");
-    const bool use_tree = TREE_ONLY || rbd_option(RBD_OPT_GRAD_KERNEL) == RBD_GRAD_KERNEL_TREE;
-    if (use_tree && lds <= 160 * 1024) {
-      const int64_t blocks = (B + 63) / 64;
-      if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B too large");
-      int rc;
-      auto k = rnea_grad_tree_kernel<T, HAS_QDD>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks, TREE_MULTI ? 1 : tree_n_roots()), dim3(64 * TREE_W), lds, (hipStream_t)stream, q, qd, qdd, gravity, use_damping, (long long)B, c, dc_du);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "rbd_rnea_grad (tree kernel) launch");
-      return 0;
-    }
-  }
-  if constexpr (TREE_ONLY || tws_only<T>()) {
-    return fail(RBD_ERR_UNSUPPORTED, "rbd_rnea_grad: no kernel");   // unreachable (static_assert / return above)
-  } else if constexpr (grad_chain_kernel<T>()) {
-    // one lane per configuration, tile-walking blocks (rbd_idsva.h)
-    return idsva_launch<T, HAS_QDD, false>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream, nullptr);
-  } else {
-    return rnea_grad_launch1<T, HAS_QDD, false>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream, nullptr);
-  }
-}
-
-template <class T>
-int rnea_grad_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                     T* c, T* dc_du, void* stream) {
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_grad: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !dc_du) return fail(RBD_ERR_ARG, "rbd_rnea_grad: q, qd and dc_du must be non-null");
-  if (((reinterpret_cast<uintptr_t>(dc_du) | reinterpret_cast<uintptr_t>(c)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_rnea_grad: output buffers must be 16-byte aligned");
-  if (qdd) return rnea_grad_launch_q<T, true>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream);
-  // qdd = None (:589): the HAS_QDD = false kernels live in the GRADN unit
-  if constexpr (sizeof(T) == 4) return rbd_grad_noqdd_f32((const float*)q, (const float*)qd, (float)gravity, use_damping, B, (float*)c, (float*)dc_du, stream);
-  else return rbd_grad_noqdd_f64((const double*)q, (const double*)qd, (double)gravity, use_damping, B, (double*)c, (double*)dc_du, stream);
-}
-
-// rnea + rnea_grad: (c, v, a, f, dc_du).  One launch when the column kernel serves the batch, otherwise the
-// rnea kernel of the RNEA unit followed by the gradient kernel on the same stream.
-template <class T>
-int rnea_with_grad_launch(const T* q, const T* qd, const T* qdd, T gravity, int use_damping, int64_t B,
-                          T* c, T* v, T* a, T* f, T* dc_du, void* stream) {
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rnea_with_grad: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !c || !v || !a || !f || !dc_du) return fail(RBD_ERR_ARG, "rbd_rnea_with_grad: q, qd, c, v, a, f, dc_du must be non-null");
-  if (((reinterpret_cast<uintptr_t>(dc_du) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(a) |
-        reinterpret_cast<uintptr_t>(f)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_rnea_with_grad: output buffers must be 16-byte aligned");
-  if (grad_use_cols<T>(B)) {
-    if (qdd) return grad_cols_launch<T, true>(q, qd, qdd, gravity, use_damping, B, c, v, a, f, dc_du, stream);
-    if constexpr (sizeof(T) == 4) return rbd_grad_cols_noqdd_f32((const float*)q, (const float*)qd, (float)gravity, use_damping, B, (float*)c, (float*)v, (float*)a, (float*)f, (float*)dc_du, stream);
-    else return rbd_grad_cols_noqdd_f64((const double*)q, (const double*)qd, (double)gravity, use_damping, B, (double*)c, (double*)v, (double*)a, (double*)f, (double*)dc_du, stream);
-  }
-  int rc;
-  if constexpr (sizeof(T) == 4) rc = rbd_rnea_f32((const float*)q, (const float*)qd, (const float*)qdd, (float)gravity, B, (float*)c, (float*)v, (float*)a, (float*)f, stream);
-  else rc = rbd_rnea_f64((const double*)q, (const double*)qd, (const double*)qdd, (double)gravity, B, (double*)c, (double*)v, (double*)a, (double*)f, stream);
-  if (rc != 0) return rc;
-  return rnea_grad_launch<T>(q, qd, qdd, gravity, use_damping, B, nullptr, dc_du, stream);
-}
-
-// name of the kernel rnea_grad_launch<T> would run (HAS_QDD = true) under the current options
-template <class T>
-int grad_kernel_name(int64_t B, char* buf, size_t len) {
-  using namespace rbdk;
-  const char* t = sizeof(T) == 4 ? "float" : "double";
-  if (grad_use_cols<T>(B)) { std::snprintf(buf, len, "rnea_grad_cols_kernel<%s,true>", t); return 0; }
-  constexpr bool TREE_ONLY = GRAD_TREE_DEFAULT && sizeof(T) == 4;
-  constexpr bool TREE_BUILT = RBD_FAST_STAGE ? TREE_ONLY : GRAD_TREE_OK && (sizeof(T) == 4 || (N <= 12 && rbdm::MAXDEPTH <= 5));   // fp64: the root path's S / psid / psidd (36 registers per body) must fit 512 VGPRs without scratch
-  bool tree = TREE_ONLY;
-  if constexpr (TREE_BUILT) tree = tree || (rbd_option(RBD_OPT_GRAD_KERNEL) == RBD_GRAD_KERNEL_TREE && tree_lds_bytes<T>() <= 160 * 1024);
-  bool tws = false;
-  if constexpr (tws_built<T>()) tws = tws_only<T>() || rbd_option(RBD_OPT_GRAD_KERNEL) == RBD_GRAD_KERNEL_TREE;
-  if (tws) std::snprintf(buf, len, "rnea_grad_tree_ws_kernel<%s,true>", t);
-  else if (tree) std::snprintf(buf, len, "rnea_grad_tree_kernel<%s,true>", t);
-  else if (grad_chain_kernel<T>()) {
-#ifndef RBD_EXP_NO_PIPE
-    if (IDS_PIPE_OK && sizeof(T) == 4) std::snprintf(buf, len, "rnea_grad_idsva_pipe_kernel<%s,true,false>", t);
-    else
-#endif
-    std::snprintf(buf, len, "rnea_grad_idsva_kernel<%s,true,false>", t);
-  }
-  else std::snprintf(buf, len, "rnea_grad_kernel<%s,true,false>", t);
-  return 0;
-}
-
-#endif  // RBD_NEED_GRAD
-
-#ifdef RBD_NEED_MINV
-template <class T>
-int minv_launch(const T* q, int64_t B, int output_dense, T* Minv, void* workspace, size_t wsb, void* stream,
-                const T* u = nullptr, const T* cbias = nullptr, T* qdd = nullptr, const T* qd = nullptr, T gravity = T(0)) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_minv: B < 0");
-  if (B == 0) return 0;
-  if (!q || (!Minv && !qdd)) return fail(RBD_ERR_ARG, "rbd_minv: q and Minv must be non-null");
-  if ((reinterpret_cast<uintptr_t>(Minv) & 15u) != 0) return fail(RBD_ERR_ARG, "rbd_minv: Minv must be 16-byte aligned");
-  if constexpr (minv_use_lane<T>()) {
-    // fused one-lane-per-configuration kernel (rbd_minv_lane.h): no workspace
-    const int64_t blocks = (B + 63) / 64;
-    if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv: B too large");
-    const size_t lds = sizeof(T) * (size_t)64 * MINV_LANE_TS;
-    auto k = minv_lane_kernel<T>;
-    int rc;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    // (qd given instead of c: the kernel computes the bias force itself, rbd_minv_lane.h)
-    if (qdd && !cbias && !qd) return fail(RBD_ERR_ARG, "rbd_minv (forward dynamics): c or qd must be given");
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, (long long)B, output_dense, Minv, u, cbias, qdd,
-                       cbias ? (const T*)nullptr : qd, gravity);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_minv launch");
-    return 0;
-  } else {
-  if (qdd && !cbias) return fail(RBD_ERR_ARG, "rbd_minv (forward dynamics): this robot's kernels need the bias force c");
-  hipStream_t s = (hipStream_t)stream;
-  const int pa = rbd_option(RBD_OPT_MINV_PHASE_A);
-  // phase A: one lane per configuration when that alone fills the chip (>= 4 waves per SIMD),
-  // otherwise eight lanes per configuration (rbd_minv_ia8.h), which also finishes the groups of <= 8 bodies
-  // a robot whose big groups have limbs: everything in one launch (rbd_minv_fused.h); measured on Atlas against the
-  // two launches: 11.5 vs 17.3 us at B = 4 096, 27.0 vs 33.8 at 16 384, 174 vs 233 at 131 072, 785 vs 928 at 524 288
-  if constexpr (MINV_FUSED_OK && mf_lds_bytes<T>() <= 160 * 1024) {
-    if (pa == RBD_MINV_PHASE_A_FUSED || pa == RBD_MINV_PHASE_A_AUTO) {
-      const int64_t nbf = mf_blocks(B);
-      if (nbf > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv: B too large");
-      constexpr size_t ldsf = mf_lds_bytes<T>();
-      auto kf = minv_fused_kernel<T>;
-      int rcf;
-      if ((rcf = ensure_lds(kf, ldsf)) != 0) return rcf;
-      hipLaunchKernelGGL(kf, dim3((unsigned)nbf), dim3(64 * MF_W), ldsf, s, q, (long long)B, output_dense, Minv, u, cbias, qdd);
-      hipError_t ef = hipGetLastError();
-      if (ef != hipSuccess) return hip_fail(ef, "rbd_minv (fused) launch");
-      return 0;
-    }
-  }
-  // the two-launch path is the only one that goes through the HBM workspace (rbd_minv_workspace_bytes reports 0
-  // when the one-launch kernel is selected)
-  const size_t need = (size_t)B * MINV_WS_PER_CFG * sizeof(T);
-  if (!workspace || wsb < need) return fail(RBD_ERR_WORKSPACE, "rbd_minv: workspace missing or smaller than rbd_minv_workspace_bytes()");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(RBD_ERR_WORKSPACE, "rbd_minv: workspace must be 16-byte aligned");
-  T* ws = reinterpret_cast<T*>(workspace);
-  const bool lane_a = pa == RBD_MINV_PHASE_A_LANE || (pa != RBD_MINV_PHASE_A_IA8 && rbd_select_batch(B) >= 64 * 1024 * 4);
-  const int64_t blocksA = (B + 63) / 64, blocksB = minv_cols_blocks(B, !lane_a);
-  if (blocksB > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_minv: B too large");
-  if (lane_a) {
-    hipLaunchKernelGGL(minv_ia_kernel<T>, dim3((unsigned)blocksA), dim3(64), 0, s, q, (long long)B, ws);
-  } else {
-    hipLaunchKernelGGL(minv_ia8_kernel<T>, dim3((unsigned)((B + 7) / 8), n_groups()), dim3(64), 0, s, q, (long long)B, ws, 1,
-                       output_dense, Minv, u, cbias, qdd);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_minv phase A launch");
-  if (blocksB > 0) {
-    constexpr size_t lds = minv_cols_lds_bytes<T>();
-    auto k = minv_cols_kernel<T>;
-    int rc;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocksB), dim3(64 * MINV_COLS_W), lds, s, (const T*)ws, (long long)B, output_dense, Minv, u, cbias,
-                       qdd, lane_a ? 0 : 1);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_minv phase B launch");
-  return 0;
-  }
-}
-
-// name of the dominant kernel minv_launch<T> would run for B rows under the current options
-template <class T>
-int minv_kernel_name(int64_t B, char* buf, size_t len) {
-  const char* t = sizeof(T) == 4 ? "float" : "double";
-  const int pa = rbd_option(RBD_OPT_MINV_PHASE_A);
-  bool fused = false;
-  if constexpr (!rbdk::minv_use_lane<T>()) {
-    if constexpr (rbdk::MINV_FUSED_OK && rbdk::mf_lds_bytes<T>() <= 160 * 1024)
-      fused = pa == RBD_MINV_PHASE_A_FUSED || pa == RBD_MINV_PHASE_A_AUTO;
-  }
-  if (rbdk::minv_use_lane<T>()) std::snprintf(buf, len, "minv_lane_kernel<%s>", t);
-  else if (fused) std::snprintf(buf, len, "minv_fused_kernel<%s>", t);
-  else std::snprintf(buf, len, "minv_cols_kernel<%s>", t);
-  return 0;
-}
-
-// does minv_launch<T> go through the HBM workspace under the current options?
-template <class T>
-int minv_needs_workspace() {
-  if constexpr (rbdk::minv_use_lane<T>()) return 0;
-  if constexpr (rbdk::MINV_FUSED_OK && rbdk::mf_lds_bytes<T>() <= 160 * 1024) {
-    const int pa = rbd_option(RBD_OPT_MINV_PHASE_A);
-    if (pa == RBD_MINV_PHASE_A_FUSED || pa == RBD_MINV_PHASE_A_AUTO) return 0;
-  }
-  return 1;
-}
-
-#endif  // RBD_NEED_MINV
-
-#if defined(RBD_TU_MINV_F32) || defined(RBD_TU_MINV_F64)
-template <class T>
-int crba_launch(const T* q, int64_t B, T* H, void* stream) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_crba: B < 0");
-  if (B == 0) return 0;
-  if (!q || !H) return fail(RBD_ERR_ARG, "rbd_crba: q and H must be non-null");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_crba: B too large");
-  const size_t lds = crba_tile_fits<T>() ? sizeof(T) * (size_t)64 * CRBA_TS : 0;
-  auto k = crba_kernel<T>;
-  int rc;
-  if ((rc = ensure_lds(k, lds)) != 0) return rc;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, (long long)B, H);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_crba launch");
-  return 0;
-}
-
-// ---- forward dynamics: compositions of the three kernels with fused epilogues ----
-#endif
-
-constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-#ifdef RBD_NEED_FD
-template <class T>
-int aba_launch(const T* q, const T* qd, const T* tau, T gravity, int64_t B, T* qdd, void* stream) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_aba: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !tau || !qdd) return fail(RBD_ERR_ARG, "rbd_aba: q, qd, tau and qdd must be non-null");
-  constexpr int lanes = ABA_PARK ? aba_lanes<T>() : 64;
-  const int64_t blocks = (B + lanes - 1) / lanes;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_aba: B too large");
-  constexpr size_t lds = aba_lds_bytes<T>();
-  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_aba: per-body state does not fit LDS for this robot size");
-  if (int rc = ensure_lds(aba_kernel<T>, lds)) return rc;
-  hipLaunchKernelGGL(aba_kernel<T>, dim3((unsigned)blocks, ABA_PARK ? n_groups() : 1), dim3(64), lds, (hipStream_t)stream, q, qd, tau,
-                     gravity, (long long)B, qdd);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_aba launch");
-  return 0;
-}
-
-#endif  // RBD_NEED_FD
-
-template <class T>
-struct FdWorkspace {
-  size_t off_minv_ws, off_c, off_minv, off_qdd, off_dcdu, total;
-  explicit FdWorkspace(int64_t B) {
-    using namespace rbdk;
-    size_t o = 0;
-    off_minv_ws = o; o += align16((size_t)B * MINV_WS_PER_CFG * sizeof(T));
-    off_c = o;       o += align16((size_t)B * N * sizeof(T));
-    // (one-chain fp32 robots keep the packed upper triangle of Minv here, in whole tiles: rbd_fd_chain.h)
-    const size_t dense = (size_t)B * N * N, packed = (size_t)((B + 63) / 64) * 64 * (N * (N + 1) / 2);
-    off_minv = o;    o += align16((dense > packed ? dense : packed) * sizeof(T));
-    off_qdd = o;     o += align16((size_t)B * N * sizeof(T));
-    off_dcdu = o;    o += GRAD_ACC_IN_REGS ? 0 : align16((size_t)B * 2 * N * N * sizeof(T));
-    total = o;
-  }
-};
-
-// rbd_fdsva_so: the caller's workspace holds the forward_dynamics_grad workspace (minv's scratch is its first part and is
-// reused by the dense minv that follows), then qdd [B, N], [fd_dq | fd_dqd] [B, N, 2N], Minv [B, N, N] and the
-// second_order_idsva tensors [B, 4, N, N, N]
-template <class T>
-struct FdsoWorkspace {
-  size_t fd_bytes, off_qdd, off_fd, off_minv, off_so, total;
-  explicit FdsoWorkspace(int64_t B) {
-    using namespace rbdk;
-    const size_t nn = (size_t)N * N;
-    size_t o = FdWorkspace<T>(B).total;
-    fd_bytes = o;
-    off_qdd = o;  o += align16((size_t)B * N * sizeof(T));
-    off_fd = o;   o += align16((size_t)B * 2 * nn * sizeof(T));
-    off_minv = o; o += align16((size_t)B * nn * sizeof(T));
-    off_so = o;   o += align16((size_t)B * 4 * nn * N * sizeof(T));
-    total = o;
-  }
-};
-// largest B whose workspace and output sizes stay far inside size_t / int64 index arithmetic
-inline int64_t fdso_max_batch() { return (int64_t)(INT64_MAX / (int64_t)(4 * (FdsoWorkspace<double>(1).total + 64))); }
-
-#ifdef RBD_NEED_FDSO
-// rbd_fdsva_so: forward_dynamics_grad (qdd, fd_dq | fd_dqd), dense minv, second_order_idsva at that qdd -- the existing
-// entry points, on the caller's stream -- then the contraction of rbd_fdsva_so.h.  Arguments are checked before any launch.
-template <class T>
-int fdso_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* out, void* workspace, size_t wsb, void* stream) {
-  using namespace rbdk;
-  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_fdsva_so: fixed-base robots only");
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_fdsva_so: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !u || !out) return fail(RBD_ERR_ARG, "rbd_fdsva_so: q, qd, u and out must be non-null");
-  constexpr int C = fdso_cfgs();
-  if (B > fdso_max_batch() || (B + C - 1) / C > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_fdsva_so: B too large");
-  const int64_t blocks = (B + C - 1) / C;
-  const FdsoWorkspace<T> L(B);
-  if (!workspace || wsb < L.total) return fail(RBD_ERR_ARG, "rbd_fdsva_so: workspace missing or smaller than rbd_fdsva_so_workspace_bytes()");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(RBD_ERR_ARG, "rbd_fdsva_so: workspace must be 16-byte aligned");
-  if constexpr (N > FDSO_MAX_N) {
-    return fail(RBD_ERR_UNSUPPORTED, "rbd_fdsva_so: robots of more than 32 bodies are not supported (one thread per (j, k) column)");
-  } else {
-    char* w = reinterpret_cast<char*>(workspace);
-    T* qdd = reinterpret_cast<T*>(w + L.off_qdd);
-    T* fd = reinterpret_cast<T*>(w + L.off_fd);
-    T* Mi = reinterpret_cast<T*>(w + L.off_minv);
-    T* so = reinterpret_cast<T*>(w + L.off_so);
-    int rc;
-    if constexpr (sizeof(T) == 4) {
-      if ((rc = rbd_forward_dynamics_grad_f32((const float*)q, (const float*)qd, (const float*)u, (float)gravity, B, (float*)qdd, (float*)fd, w, L.fd_bytes, stream)) != 0) return rc;
-      if ((rc = rbd_minv_f32((const float*)q, B, 1, (float*)Mi, w, L.fd_bytes, stream)) != 0) return rc;
-      if ((rc = rbd_second_order_idsva_f32((const float*)q, (const float*)qd, (const float*)qdd, (float)gravity, B, (float*)so, stream)) != 0) return rc;
-    } else {
-      if ((rc = rbd_forward_dynamics_grad_f64((const double*)q, (const double*)qd, (const double*)u, (double)gravity, B, (double*)qdd, (double*)fd, w, L.fd_bytes, stream)) != 0) return rc;
-      if ((rc = rbd_minv_f64((const double*)q, B, 1, (double*)Mi, w, L.fd_bytes, stream)) != 0) return rc;
-      if ((rc = rbd_second_order_idsva_f64((const double*)q, (const double*)qd, (const double*)qdd, (double)gravity, B, (double*)so, stream)) != 0) return rc;
-    }
-    const dim3 grid((unsigned)blocks), block(fdso_threads());
-    hipStream_t s = (hipStream_t)stream;
-    constexpr int G = fdso_group<T>();
-    if constexpr (G == 4) {
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 15>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-    } else if constexpr (G == 2) {
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 3>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 12>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-    } else {
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 1>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 2>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 4>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-      hipLaunchKernelGGL((fdso_contract_kernel<T, 8>), grid, block, 0, s, (const T*)Mi, (const T*)fd, (const T*)so, (long long)B, out);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "rbd_fdsva_so contraction launch");
-  }
-}
-#endif  // RBD_NEED_FDSO
-
-#ifdef RBD_NEED_ROLL
-// rbd_rollout: one launch for all T steps (rbd_rollout.h).  Arguments are checked before the launch.
-template <class T>
-int rollout_launch(const T* q0, const T* qd0, const T* u, int u_shared, T dt, T gravity, int integrator, int64_t B, int64_t steps,
-                   T* q_out, T* qd_out, int trajectory, void* stream) {
-  using namespace rbdk;
-  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: fixed-base robots only");
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_rollout: B < 0");
-  if (steps < 0) return fail(RBD_ERR_ARG, "rbd_rollout: T < 0");
-  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "rbd_rollout: dt must be finite");
-  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
-    return fail(RBD_ERR_ARG, "rbd_rollout: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)");
-  if (B == 0 || steps == 0) return 0;
-  if (!q0 || !qd0 || !u || !q_out || !qd_out) return fail(RBD_ERR_ARG, "rbd_rollout: q0, qd0, u, q_out and qd_out must be non-null");
-  if (((reinterpret_cast<uintptr_t>(q_out) | reinterpret_cast<uintptr_t>(qd_out)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_rollout: output buffers must be 16-byte aligned");
-  constexpr int lanes = ABA_PARK ? roll_lanes<T>() : 64;
-  const int64_t blocks = (B + lanes - 1) / lanes;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_rollout: B too large");
-  // B T n elements of u and of each trajectory: byte offsets stay far inside int64
-  if (steps > (INT64_MAX / 64) / (B * N)) return fail(RBD_ERR_ARG, "rbd_rollout: B * T * n too large");
-  constexpr size_t lds = roll_lds_bytes<T>();
-  if (lds > 160 * 1024) return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: per-body state does not fit LDS for this robot size");
-  if (int rc = ensure_lds(rollout_kernel<T>, lds)) return rc;
-  const long long row = (long long)B * N;
-  const int aligned = (row * (long long)sizeof(T)) % 16 == 0;      // every trajectory slice starts on a 16-byte boundary
-  hipLaunchKernelGGL(rollout_kernel<T>, dim3((unsigned)blocks, ABA_PARK ? n_groups() : 1), dim3(64), lds, (hipStream_t)stream, q0, qd0,
-                     u, u_shared ? (long long)N : row, u_shared ? 1 : 0, dt, gravity, integrator, (long long)B, (long long)steps,
-                     q_out, qd_out, trajectory ? row : 0LL, aligned);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "rbd_rollout launch");
-  return 0;
-}
-#endif  // RBD_NEED_ROLL
-
-#ifdef RBD_NEED_FD
-template <class T>
-int fd_launch(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, bool want_grad,
-              void* workspace, size_t wsb, void* stream) {
-  using namespace rbdk;
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_forward_dynamics: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !u) return fail(RBD_ERR_ARG, "rbd_forward_dynamics: q, qd, u must be non-null");
-  if (want_grad ? !dqdd_du : !qdd) return fail(RBD_ERR_ARG, "rbd_forward_dynamics: output pointer is null");
-  // refused HERE, before the first of the three launches (the gradient launcher's own check would come after two of them)
-  if (((reinterpret_cast<uintptr_t>(qdd) | reinterpret_cast<uintptr_t>(dqdd_du)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_forward_dynamics: output buffers must be 16-byte aligned");
-  // qdd alone: the articulated-body sweep gives Minv (u - c) (:1372-1374) without forming Minv or c
-  // (one launch, no workspace; 47 vs 76 us for the 7-DoF arm at B = 1M)
-  if (!want_grad) return aba_launch<T>(q, qd, u, gravity, B, qdd, stream);
-  const FdWorkspace<T> L(B);
-  if (!workspace || wsb < L.total) return fail(RBD_ERR_WORKSPACE, "rbd_forward_dynamics: workspace missing or smaller than rbd_fd_workspace_bytes()");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(RBD_ERR_WORKSPACE, "rbd_forward_dynamics: workspace must be 16-byte aligned");
-  char* w = reinterpret_cast<char*>(workspace);
-  T* c = reinterpret_cast<T*>(w + L.off_c);
-  T* Mi = reinterpret_cast<T*>(w + L.off_minv);
-  T* qdd_buf = qdd ? qdd : reinterpret_cast<T*>(w + L.off_qdd);
-  int rc;
-  if constexpr (fd_chain_ok<T>() && grad_chain_kernel<T>()) {
-    // one chain (rbd_fd_chain.h): fd_pre_kernel (bias force, Minv, qdd in one lane; Minv's upper triangle to a lane-major
-    // workspace), then the world-frame chain gradient kernel with the -Minv product on its finished entries -- the
-    // software-pipelined kernel in fp32 where it applies
-    const int64_t tiles = (B + 63) / 64;
-    if (tiles > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: B too large");
-    hipLaunchKernelGGL(fd_pre_kernel<T>, dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, q, qd, u, gravity, (long long)B, qdd_buf, Mi);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_forward_dynamics_grad (fd_pre_kernel) launch");
-    const size_t lds = sizeof(T) * (size_t)64 * IDS_TS;
-    int resident = 0;
-    const int kflags = chain_kernel_flags<T>(0, B, false);
-#ifndef RBD_EXP_NO_PIPE
-    if constexpr (IDS_PIPE_OK && sizeof(T) == 4) {
-      auto kp = rnea_grad_idsva_pipe_kernel<T, true, true>;
-      if ((rc = ensure_lds(kp, lds)) != 0) return rc;
-      if ((rc = resident_blocks(kp, 64, lds, &resident)) != 0) return rc;
-      const int64_t blocks = tiles < resident ? tiles : resident;
-      hipLaunchKernelGGL(kp, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, kflags, (long long)B,
-                         (T*)nullptr, dqdd_du, (const T*)Mi);
-    } else
-#endif
-    {
-      auto k = rnea_grad_idsva_kernel<T, true, true>;
-      if ((rc = ensure_lds(k, lds)) != 0) return rc;
-      if ((rc = resident_blocks(k, 64, lds, &resident)) != 0) return rc;
-      const int64_t blocks = tiles < resident ? tiles : resident;
-      hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, q, qd, (const T*)qdd_buf, gravity, kflags, (long long)B,
-                         (T*)nullptr, dqdd_du, (const T*)Mi);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_forward_dynamics_grad (gradient kernel) launch");
-    return 0;
-  } else {
-  // c = rnea(q, qd) with qdd = None (:1372): the c-only kernel of the RNEA unit -- or, where the one-lane minv kernel serves the
-  // robot, no launch at all: that kernel computes the bias force of its groups from qd itself (rbd_minv_lane.h)
-  constexpr bool bias_in_minv = minv_use_lane<T>();
-  if constexpr (!bias_in_minv) {
-    if constexpr (sizeof(T) == 4) rc = rbd_rnea_f32((const float*)q, (const float*)qd, nullptr, (float)gravity, B, (float*)c, nullptr, nullptr, nullptr, stream);
-    else rc = rbd_rnea_f64((const double*)q, (const double*)qd, nullptr, (double)gravity, B, (double*)c, nullptr, nullptr, nullptr, stream);
-    if (rc != 0) return rc;
-  }
-  const T* cb = bias_in_minv ? nullptr : c;
-  // qdd = Minv (u - c) (:1373-1374), fused into the last phase of minv (MINV unit)
-  if constexpr (sizeof(T) == 4) rc = rbd_minv_fd_f32((const float*)q, B, (float*)Mi, w + L.off_minv_ws, (size_t)B * MINV_WS_PER_CFG * sizeof(T), stream, (const float*)u, (const float*)cb, (float*)qdd_buf, (const float*)qd, (float)gravity);
-  else rc = rbd_minv_fd_f64((const double*)q, B, (double*)Mi, w + L.off_minv_ws, (size_t)B * MINV_WS_PER_CFG * sizeof(T), stream, (const double*)u, (const double*)cb, (double*)qdd_buf, (const double*)qd, (double)gravity);
-  if (rc != 0) return rc;
-  if (!want_grad) return 0;
-  // [qdd_dq | qdd_dqd] = -Minv rnea_grad(q, qd, qdd) (:1378-1383)
-  if constexpr (GRAD_ACC_IN_REGS) {
-    return rnea_grad_launch1<T, true, true>(q, qd, qdd_buf, gravity, 0, B, nullptr, dqdd_du, stream, Mi);
-  } else {
-    T* dc = reinterpret_cast<T*>(w + L.off_dcdu);
-    // plain rnea_grad of the GRAD unit, then the -Minv product
-    if constexpr (sizeof(T) == 4) rc = rbd_rnea_grad_f32((const float*)q, (const float*)qd, (const float*)qdd_buf, (float)gravity, 0, B, nullptr, (float*)dc, stream);
-    else rc = rbd_rnea_grad_f64((const double*)q, (const double*)qd, (const double*)qdd_buf, (double)gravity, 0, B, nullptr, (double*)dc, stream);
-    if (rc != 0) return rc;
-    constexpr int MMC = negmm_cfgs<T, N>();
-    const int64_t ablocks = (B + MMC - 1) / MMC;
-    if (ablocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_forward_dynamics_grad: B too large");
-    hipLaunchKernelGGL((neg_mm_kernel<T, N>), dim3((unsigned)ablocks), dim3(negmm_threads<T, N>()), 0, (hipStream_t)stream,
-                       (const T*)Mi, (const T*)dc, (long long)B, dqdd_du);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "rbd_forward_dynamics_grad apply launch");
-    return 0;
-  }
-  }
-}
-#endif  // RBD_NEED_FD
-
-#ifdef RBD_NEED_EE
-// rbd_ee_pose: site table (host arrays) -> EeSites kernel argument; one launch for pose, gradient or both
-template <class T>
-int ee_launch(const T* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
-              T* pose, T* dpose, void* stream) {
-  using namespace rbdk;
-  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_ee_pose: fixed-base robots only");
-  if (n_sites < 1 || n_sites > RBD_EE_MAX_SITES) return fail(RBD_ERR_ARG, "rbd_ee_pose: n_sites must be in [1, RBD_EE_MAX_SITES]");
-  if (!site_body || !site_T || !offset) return fail(RBD_ERR_ARG, "rbd_ee_pose: site_body, site_T and offset must be non-null");
-  EeSites<T> st;
-  std::memset(&st, 0, sizeof(st));
-  st.n_sites = n_sites;
-  const double w = offset[3];
-  st.w = (T)w;
-  for (int s = 0; s < n_sites; ++s) {
-    if (site_body[s] < 0 || site_body[s] >= rbdm::N) return fail(RBD_ERR_ARG, "rbd_ee_pose: site body id out of range");
-    st.body[s] = site_body[s];
-    const double* M = site_T + 12 * s;              // [R | t] row-major 3 x 4
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) st.M[s][3 * r + c] = (T)M[4 * r + c];
-      st.pl[s][r] = (T)(M[4 * r] * offset[0] + M[4 * r + 1] * offset[1] + M[4 * r + 2] * offset[2] + w * M[4 * r + 3]);
-    }
-  }
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_ee_pose: B < 0");
-  if (B == 0) return 0;                             // (empty outputs may come as null pointers)
-  if (!q) return fail(RBD_ERR_ARG, "rbd_ee_pose: q must be non-null");
-  if (!pose && !dpose) return fail(RBD_ERR_ARG, "rbd_ee_pose: pose and dpose are both null");
-  if (((reinterpret_cast<uintptr_t>(pose) | reinterpret_cast<uintptr_t>(dpose)) & 15u) != 0)
-    return fail(RBD_ERR_ARG, "rbd_ee_pose: output buffers must be 16-byte aligned");
-  const int64_t blocks = (B + 63) / 64;
-  if (blocks > 0x7fffffffLL) return fail(RBD_ERR_ARG, "rbd_ee_pose: B too large");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds = ee_lds_bytes<T>(n_sites, pose != nullptr, dpose != nullptr);
-  if (lds > 160 * 1024)             // (a robot near RBD_MAX_BODIES in fp64: its [64][6n] gradient tile alone)
-    return fail(RBD_ERR_UNSUPPORTED, "rbd_ee_pose: the q / pose / gradient tiles exceed the 160 KB of LDS of a CU for this "
-                                     "robot and precision; pass fewer sites per call");
-  int rc;
-  if (pose && dpose) {
-    auto k = ee_pose_kernel<T, true, true>;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
-  } else if (pose) {
-    auto k = ee_pose_kernel<T, true, false>;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
-  } else {
-    auto k = ee_pose_kernel<T, false, true>;
-    if ((rc = ensure_lds(k, lds)) != 0) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64), lds, s, q, (long long)B, st, pose, dpose);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_ee_pose launch");
-}
-#endif  // RBD_NEED_EE
-
-#ifdef RBD_NEED_SO
-// rbd_second_order_idsva: out [B, 4, N, N, N]; arguments checked before anything touches the GPU
-template <class T>
-int so_launch(const T* q, const T* qd, const T* qdd, T gravity, int64_t B, T* out, void* stream) {
-  using namespace rbdk;
-  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "rbd_second_order_idsva: fixed-base robots only");
-  if (B < 0) return fail(RBD_ERR_ARG, "rbd_second_order_idsva: B < 0");
-  if (B == 0) return 0;
-  if (!q || !qd || !qdd || !out) return fail(RBD_ERR_ARG, "rbd_second_order_idsva: q, qd, qdd and out must be non-null");
-  constexpr int G = so_configs_per_block<T>();
-  const int64_t blocks = (B + G - 1) / G;
-  if (blocks > 0x7fffffffLL || B > (int64_t)(INT64_MAX / SO_PER_CFG))
-    return fail(RBD_ERR_ARG, "rbd_second_order_idsva: B too large");
-  hipLaunchKernelGGL(so_idsva_kernel<T>, dim3((unsigned)blocks), dim3(SO_THREADS), 0, (hipStream_t)stream, q, qd, qdd,
-                     gravity, (long long)B, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, "rbd_second_order_idsva launch");
-}
-#endif  // RBD_NEED_SO
-
-#if defined(RBD_TU_PASS_F32) || defined(RBD_TU_PASS_F64)
-// ---- per-pass entry points (rbd_passes.h) ------------------------------------------------------------
-int pass_blocks(int64_t B, const char* who, unsigned* blocks) {
-  if (B < 0) { std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: B < 0", who); return RBD_ERR_ARG; }
-  const int64_t nb = (B + 63) / 64;
-  if (nb > 0x7fffffffLL) { std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: B too large", who); return RBD_ERR_ARG; }
-  *blocks = (unsigned)nb;
-  return 0;
-}
-int pass_done(const char* who) {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : hip_fail(e, who);
-}
-template <class T, bool DQ>
-int grad_fpass_launch(const T* q, const T* qd, const T* v, const T* a, T gravity, int64_t B, T* dv, T* da, T* df, void* stream) {
-  const char* who = DQ ? "rbd_rnea_grad_fpass_dq" : "rbd_rnea_grad_fpass_dqd";
-  unsigned blocks;
-  if (int rc = pass_blocks(B, who, &blocks)) return rc;
-  if (B == 0) return 0;
-  if (!q || !qd || !v || (DQ && !a) || !dv || !da || !df) {
-    std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: null pointer argument", who);
-    return RBD_ERR_ARG;
-  }
-  hipLaunchKernelGGL((rbdk::grad_fpass_kernel<T, DQ>), dim3(blocks), dim3(64), 0, (hipStream_t)stream, q, qd, v, a, gravity,
-                     (long long)B, dv, da, df);
-  return pass_done(who);
-}
-template <class T, bool DQ>
-int grad_bpass_launch(const T* q, const T* f, T* df, int use_damping, int64_t B, T* dc, void* stream) {
-  const char* who = DQ ? "rbd_rnea_grad_bpass_dq" : "rbd_rnea_grad_bpass_dqd";
-  unsigned blocks;
-  if (int rc = pass_blocks(B, who, &blocks)) return rc;
-  if (B == 0) return 0;
-  if (!q || (DQ && !f) || !df || !dc) {
-    std::snprintf(rbd_err_buf(), RBD_ERR_LEN, "%s: null pointer argument", who);
-    return RBD_ERR_ARG;
-  }
-  hipLaunchKernelGGL((rbdk::grad_bpass_kernel<T, DQ>), dim3(blocks), dim3(64), 0, (hipStream_t)stream, q, f, df, use_damping,
-                     (long long)B, dc);
-  return pass_done(who);
-}
-template <class T>
-int minv_bpass_launch(const T* q, int64_t B, T* Minv, T* F, T* U, T* D, void* stream) {
-  unsigned blocks;
-  if (int rc = pass_blocks(B, "rbd_minv_bpass", &blocks)) return rc;
-  if (B == 0) return 0;
-  if (!q || !Minv || !F || !U || !D) return fail(RBD_ERR_ARG, "rbd_minv_bpass: null pointer argument");
-  hipLaunchKernelGGL(rbdk::minv_bpass_kernel<T>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, q, (long long)B, Minv, F, U, D);
-  return pass_done("rbd_minv_bpass");
-}
-template <class T>
-int minv_fpass_launch(const T* q, int64_t B, T* Minv, T* F, const T* U, const T* D, void* stream) {
-  unsigned blocks;
-  if (int rc = pass_blocks(B, "rbd_minv_fpass", &blocks)) return rc;
-  if (B == 0) return 0;
-  if (!q || !Minv || !F || !U || !D) return fail(RBD_ERR_ARG, "rbd_minv_fpass: null pointer argument");
-  hipLaunchKernelGGL(rbdk::minv_fpass_kernel<T>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, q, (long long)B, Minv, F, U, D);
-  return pass_done("rbd_minv_fpass");
-}
-#endif
-}  // namespace
-
-extern "C" {
-
-// kernel names: every family unit answers for its own kernels (the selection logic lives there)
-__attribute__((visibility("hidden"))) int rbd_grad_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_grad_kernel_name_f64(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_minv_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_minv_kernel_name_f64(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f32(void);
-__attribute__((visibility("hidden"))) int rbd_minv_needs_ws_f64(void);
-__attribute__((visibility("hidden"))) int rbd_rnea_kernel_name_f32(int64_t B, char* buf, size_t len);
-__attribute__((visibility("hidden"))) int rbd_rnea_kernel_name_f64(int64_t B, char* buf, size_t len);
-#ifdef RBD_TU_RNEA_F32
-int rbd_rnea_kernel_name_f32(int64_t B, char* buf, size_t len) { return rnea_kernel_name<float>(B, buf, len); }
-#endif
-#ifdef RBD_TU_RNEA_F64
-int rbd_rnea_kernel_name_f64(int64_t B, char* buf, size_t len) { return rnea_kernel_name<double>(B, buf, len); }
-#endif
-#ifdef RBD_TU_GRAD_F32
-int rbd_grad_kernel_name_f32(int64_t B, char* buf, size_t len) { return grad_kernel_name<float>(B, buf, len); }
-#endif
-#ifdef RBD_TU_GRAD_F64
-int rbd_grad_kernel_name_f64(int64_t B, char* buf, size_t len) { return grad_kernel_name<double>(B, buf, len); }
-#endif
-#ifdef RBD_TU_MINV_F32
-int rbd_minv_kernel_name_f32(int64_t B, char* buf, size_t len) { return minv_kernel_name<float>(B, buf, len); }
-int rbd_minv_needs_ws_f32(void) { return minv_needs_workspace<float>(); }
-#endif
-#ifdef RBD_TU_MINV_F64
-int rbd_minv_kernel_name_f64(int64_t B, char* buf, size_t len) { return minv_kernel_name<double>(B, buf, len); }
-int rbd_minv_needs_ws_f64(void) { return minv_needs_workspace<double>(); }
-#endif
-
-#ifdef RBD_TU_COMMON
-int rbd_abi_version(void) { return RBD_ABI_VERSION; }
-const char* rbd_last_error(void) { return rbd_err_buf(); }
-
-int rbd_set_option(int option, int value) {
-  std::atomic<int>* s = rbd_option_slot(option);
-  if (!s) return fail(RBD_ERR_ARG, "rbd_set_option: unknown option");
-  if (value < 0 || (option != RBD_OPT_SELECT_BATCH && value > (option == RBD_OPT_RNEA_KERNEL ? 2 : 3)))
-    return fail(RBD_ERR_ARG, "rbd_set_option: value out of range");
-  s->store(value, std::memory_order_relaxed);
-  return 0;
-}
-int rbd_get_option(int option) {
-  std::atomic<int>* s = rbd_option_slot(option);
-  return s ? s->load(std::memory_order_relaxed) : RBD_ERR_ARG;
-}
-int rbd_kernel_name(int op, int elem_size, int64_t B, char* buf, size_t len) {
-  if (!buf || len == 0 || (elem_size != 4 && elem_size != 8)) return fail(RBD_ERR_ARG, "rbd_kernel_name: bad arguments");
-  switch (op) {
-    case RBD_OP_RNEA:
-      return elem_size == 4 ? rbd_rnea_kernel_name_f32(B, buf, len) : rbd_rnea_kernel_name_f64(B, buf, len);
-    case RBD_OP_RNEA_GRAD:
-      return elem_size == 4 ? rbd_grad_kernel_name_f32(B, buf, len) : rbd_grad_kernel_name_f64(B, buf, len);
-    case RBD_OP_MINV:
-      return elem_size == 4 ? rbd_minv_kernel_name_f32(B, buf, len) : rbd_minv_kernel_name_f64(B, buf, len);
-    default:
-      return fail(RBD_ERR_ARG, "rbd_kernel_name: unknown op");
-  }
-}
-
-int rbd_model_info(rbd_model_info_t* out) {
-  if (!out) return fail(RBD_ERR_ARG, "rbd_model_info: out is null");
-  std::memset(out, 0, sizeof(*out));
-  out->abi_version = RBD_ABI_VERSION;
-  out->n = rbdm::N;
-  out->max_depth = rbdm::MAXDEPTH;
-  out->hash = RBD_MODEL_HASH;
-  out->floating_base = rbdm::FLOATING_BASE ? 1 : 0;
-  out->nv = rbdm::NV;
-  std::snprintf(out->name, sizeof(out->name), "%s", RBD_MODEL_NAME);
-  for (int i = 0; i < rbdm::N && i < RBD_MAX_BODIES; ++i) {
-    out->parent[i] = rbdm::PARENT[i];
-    out->joint_type[i] = rbdm::JTYPE[i];
-    out->joint_axis[i] = rbdm::AXIS[i];
-  }
-  return 0;
-}
-size_t rbd_minv_workspace_bytes(int64_t B, int elem_size) {
-  if (B <= 0 || (elem_size != 4 && elem_size != 8)) return 0;
-  if (rbdm::FLOATING_BASE) return 0;
-  // none when the kernel selected by the current RBD_OPT_MINV_PHASE_A runs without it (the one-lane kernel, the
-  // one-launch kernel): query again after changing that option
-  if (!(elem_size == 4 ? rbd_minv_needs_ws_f32() : rbd_minv_needs_ws_f64())) return 0;
-  return (size_t)B * rbdk::MINV_WS_PER_CFG * (size_t)elem_size;
-}
-size_t rbd_fd_workspace_bytes(int64_t B, int elem_size) {
-  if (B <= 0) return 0;
-  if (rbdm::FLOATING_BASE) {      // c [B, NV] | Minv [B, NV, NV] | qdd [B, NV] | dc_du [B, NV, 2 NV]  (rbd_fb_kernels.hip; the
-    if (elem_size != 4 && elem_size != 8) return 0;   // last two serve forward_dynamics_grad only)
-    return align16((size_t)B * rbdm::NV * elem_size) + align16((size_t)B * rbdm::NV * rbdm::NV * elem_size) +
-           align16((size_t)B * rbdm::NV * elem_size) + align16((size_t)B * rbdm::NV * 2 * rbdm::NV * elem_size);
-  }
-  if (elem_size == 4) return FdWorkspace<float>(B).total;
-  if (elem_size == 8) return FdWorkspace<double>(B).total;
-  return 0;
-}
-size_t rbd_fdsva_so_workspace_bytes(int64_t B, int elem_size) {
-  if (B <= 0 || rbdm::FLOATING_BASE || B > fdso_max_batch()) return 0;
-  if (elem_size == 4) return FdsoWorkspace<float>(B).total;
-  if (elem_size == 8) return FdsoWorkspace<double>(B).total;
-  return 0;
-}
-#endif
-#ifdef RBD_TU_RNEA_F32
-int rbd_rnea_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B,
-                 float* c, float* v, float* a, float* f, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_launch<float>(q, qd, qdd, gravity, B, c, v, a, f, stream);
-}
-#endif
-#ifdef RBD_TU_RNEA_F32
-int rbd_rnea_fpass_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B,
-                       float* v, float* a, float* f, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_launch<float>(q, qd, qdd, gravity, B, nullptr, v, a, f, stream, 1);
-}
-int rbd_rnea_bpass_f32(const float* q, float* f, int64_t B, float* c, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_bpass_launch<float>(q, f, B, c, stream);
-}
-#endif
-#ifdef RBD_TU_RNEA_F64
-int rbd_rnea_fpass_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B,
-                       double* v, double* a, double* f, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_launch<double>(q, qd, qdd, gravity, B, nullptr, v, a, f, stream, 1);
-}
-int rbd_rnea_bpass_f64(const double* q, double* f, int64_t B, double* c, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_bpass_launch<double>(q, f, B, c, stream);
-}
-#endif
-#ifdef RBD_TU_RNEA_F64
-int rbd_rnea_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B,
-                 double* c, double* v, double* a, double* f, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_launch<double>(q, qd, qdd, gravity, B, c, v, a, f, stream);
-}
-#endif
-#ifdef RBD_TU_GRADN_F32
-int rbd_grad_noqdd_f32(const float* q, const float* qd, float gravity, int use_damping, int64_t B, float* c, float* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_grad_launch_q<float, false>(q, qd, nullptr, gravity, use_damping, B, c, dc_du, stream);
-}
-int rbd_grad_cols_noqdd_f32(const float* q, const float* qd, float gravity, int use_damping, int64_t B, float* c, float* v, float* a, float* f, float* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_cols_launch<float, false>(q, qd, nullptr, gravity, use_damping, B, c, v, a, f, dc_du, stream);
-}
-#endif
-#ifdef RBD_TU_GRADN_F64
-int rbd_grad_noqdd_f64(const double* q, const double* qd, double gravity, int use_damping, int64_t B, double* c, double* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_grad_launch_q<double, false>(q, qd, nullptr, gravity, use_damping, B, c, dc_du, stream);
-}
-int rbd_grad_cols_noqdd_f64(const double* q, const double* qd, double gravity, int use_damping, int64_t B, double* c, double* v, double* a, double* f, double* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_cols_launch<double, false>(q, qd, nullptr, gravity, use_damping, B, c, v, a, f, dc_du, stream);
-}
-#endif
-#ifdef RBD_TU_GRAD_F32
-int rbd_rnea_grad_f32(const float* q, const float* qd, const float* qdd, float gravity,
-                      int use_damping, int64_t B, float* c, float* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_grad_launch<float>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream);
-}
-#endif
-#ifdef RBD_TU_GRAD_F64
-int rbd_rnea_grad_f64(const double* q, const double* qd, const double* qdd, double gravity,
-                      int use_damping, int64_t B, double* c, double* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_grad_launch<double>(q, qd, qdd, gravity, use_damping, B, c, dc_du, stream);
-}
-int rbd_rnea_with_grad_f64(const double* q, const double* qd, const double* qdd, double gravity, int use_damping, int64_t B,
-                           double* c, double* v, double* a, double* f, double* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_with_grad_launch<double>(q, qd, qdd, gravity, use_damping, B, c, v, a, f, dc_du, stream);
-}
-#endif
-#ifdef RBD_TU_GRAD_F32
-int rbd_rnea_with_grad_f32(const float* q, const float* qd, const float* qdd, float gravity, int use_damping, int64_t B,
-                           float* c, float* v, float* a, float* f, float* dc_du, void* stream) {
-  RbdStreamDevice sd_(stream); return rnea_with_grad_launch<float>(q, qd, qdd, gravity, use_damping, B, c, v, a, f, dc_du, stream);
-}
-#endif
-#ifdef RBD_TU_MINV_F32
-int rbd_crba_f32(const float* q, int64_t B, float* H, void* stream) { RbdStreamDevice sd_(stream); return crba_launch<float>(q, B, H, stream); }
-#endif
-#ifdef RBD_TU_MINV_F64
-int rbd_crba_f64(const double* q, int64_t B, double* H, void* stream) { RbdStreamDevice sd_(stream); return crba_launch<double>(q, B, H, stream); }
-#endif
-#ifdef RBD_TU_MINV_F32
-int rbd_minv_f32(const float* q, int64_t B, int output_dense, float* Minv, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_launch<float>(q, B, output_dense, Minv, workspace, workspace_bytes, stream);
-}
-int rbd_minv_fd_f32(const float* q, int64_t B, float* Minv, void* workspace, size_t wsb, void* stream,
-                    const float* u, const float* c, float* qdd, const float* qd, float gravity) {
-  RbdStreamDevice sd_(stream); return minv_launch<float>(q, B, 1, Minv, workspace, wsb, stream, u, c, qdd, qd, gravity);
-}
-#endif
-#ifdef RBD_TU_FD_F32
-int rbd_aba_f32(const float* q, const float* qd, const float* tau, float gravity, int64_t B, float* qdd, void* stream) {
-  RbdStreamDevice sd_(stream); return aba_launch<float>(q, qd, tau, gravity, B, qdd, stream);
-}
-int rbd_forward_dynamics_f32(const float* q, const float* qd, const float* u, float gravity, int64_t B,
-                             float* qdd, void* workspace, size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fd_launch<float>(q, qd, u, gravity, B, qdd, nullptr, false, workspace, workspace_bytes, stream);
-}
-int rbd_forward_dynamics_grad_f32(const float* q, const float* qd, const float* u, float gravity, int64_t B,
-                                  float* qdd, float* dqdd_du, void* workspace, size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fd_launch<float>(q, qd, u, gravity, B, qdd, dqdd_du, true, workspace, workspace_bytes, stream);
-}
-#endif
-#ifdef RBD_TU_FD_F64
-int rbd_aba_f64(const double* q, const double* qd, const double* tau, double gravity, int64_t B, double* qdd, void* stream) {
-  RbdStreamDevice sd_(stream); return aba_launch<double>(q, qd, tau, gravity, B, qdd, stream);
-}
-int rbd_forward_dynamics_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B,
-                             double* qdd, void* workspace, size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fd_launch<double>(q, qd, u, gravity, B, qdd, nullptr, false, workspace, workspace_bytes, stream);
-}
-int rbd_forward_dynamics_grad_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B,
-                                  double* qdd, double* dqdd_du, void* workspace, size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fd_launch<double>(q, qd, u, gravity, B, qdd, dqdd_du, true, workspace, workspace_bytes, stream);
-}
-#endif
-#ifdef RBD_TU_MINV_F64
-int rbd_minv_f64(const double* q, int64_t B, int output_dense, double* Minv, void* workspace,
-                 size_t workspace_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_launch<double>(q, B, output_dense, Minv, workspace, workspace_bytes, stream);
-}
-int rbd_minv_fd_f64(const double* q, int64_t B, double* Minv, void* workspace, size_t wsb, void* stream,
-                    const double* u, const double* c, double* qdd, const double* qd, double gravity) {
-  RbdStreamDevice sd_(stream); return minv_launch<double>(q, B, 1, Minv, workspace, wsb, stream, u, c, qdd, qd, gravity);
-}
-#endif
-
-#ifdef RBD_TU_PASS_F32
-int rbd_rnea_grad_fpass_dq_f32(const float* q, const float* qd, const float* v, const float* a, float gravity, int64_t B,
-                               float* dv_dq, float* da_dq, float* df_dq, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_fpass_launch<float, true>(q, qd, v, a, gravity, B, dv_dq, da_dq, df_dq, stream);
-}
-int rbd_rnea_grad_fpass_dqd_f32(const float* q, const float* qd, const float* v, int64_t B, float* dv_dqd, float* da_dqd,
-                                float* df_dqd, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_fpass_launch<float, false>(q, qd, v, nullptr, float(0), B, dv_dqd, da_dqd, df_dqd, stream);
-}
-int rbd_rnea_grad_bpass_dq_f32(const float* q, const float* f, float* df_dq, int64_t B, float* dc_dq, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_bpass_launch<float, true>(q, f, df_dq, 0, B, dc_dq, stream);
-}
-int rbd_rnea_grad_bpass_dqd_f32(const float* q, float* df_dqd, int use_damping, int64_t B, float* dc_dqd, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_bpass_launch<float, false>(q, nullptr, df_dqd, use_damping, B, dc_dqd, stream);
-}
-int rbd_minv_bpass_f32(const float* q, int64_t B, float* Minv, float* F, float* U, float* Dinv, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_bpass_launch<float>(q, B, Minv, F, U, Dinv, stream);
-}
-int rbd_minv_fpass_f32(const float* q, int64_t B, float* Minv, float* F, const float* U, const float* Dinv, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_fpass_launch<float>(q, B, Minv, F, U, Dinv, stream);
-}
-#endif
-#ifdef RBD_TU_PASS_F64
-int rbd_rnea_grad_fpass_dq_f64(const double* q, const double* qd, const double* v, const double* a, double gravity, int64_t B,
-                               double* dv_dq, double* da_dq, double* df_dq, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_fpass_launch<double, true>(q, qd, v, a, gravity, B, dv_dq, da_dq, df_dq, stream);
-}
-int rbd_rnea_grad_fpass_dqd_f64(const double* q, const double* qd, const double* v, int64_t B, double* dv_dqd, double* da_dqd,
-                                double* df_dqd, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_fpass_launch<double, false>(q, qd, v, nullptr, double(0), B, dv_dqd, da_dqd, df_dqd, stream);
-}
-int rbd_rnea_grad_bpass_dq_f64(const double* q, const double* f, double* df_dq, int64_t B, double* dc_dq, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_bpass_launch<double, true>(q, f, df_dq, 0, B, dc_dq, stream);
-}
-int rbd_rnea_grad_bpass_dqd_f64(const double* q, double* df_dqd, int use_damping, int64_t B, double* dc_dqd, void* stream) {
-  RbdStreamDevice sd_(stream); return grad_bpass_launch<double, false>(q, nullptr, df_dqd, use_damping, B, dc_dqd, stream);
-}
-int rbd_minv_bpass_f64(const double* q, int64_t B, double* Minv, double* F, double* U, double* Dinv, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_bpass_launch<double>(q, B, Minv, F, U, Dinv, stream);
-}
-int rbd_minv_fpass_f64(const double* q, int64_t B, double* Minv, double* F, const double* U, const double* Dinv, void* stream) {
-  RbdStreamDevice sd_(stream); return minv_fpass_launch<double>(q, B, Minv, F, U, Dinv, stream);
-}
-#endif
-#ifdef RBD_TU_EE_F32
-int rbd_ee_pose_f32(const float* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
-                    float* pose, float* dpose, void* stream) {
-  RbdStreamDevice sd_(stream); return ee_launch<float>(q, B, site_body, site_T, offset, n_sites, pose, dpose, stream);
-}
-#endif
-#ifdef RBD_TU_SO_F32
-int rbd_second_order_idsva_f32(const float* q, const float* qd, const float* qdd, float gravity, int64_t B, float* out,
-                               void* stream) {
-  RbdStreamDevice sd_(stream); return so_launch<float>(q, qd, qdd, gravity, B, out, stream);
-}
-#endif
-#ifdef RBD_TU_SO_F64
-int rbd_second_order_idsva_f64(const double* q, const double* qd, const double* qdd, double gravity, int64_t B, double* out,
-                               void* stream) {
-  RbdStreamDevice sd_(stream); return so_launch<double>(q, qd, qdd, gravity, B, out, stream);
-}
-#endif
-#ifdef RBD_TU_FDSO_F32
-int rbd_fdsva_so_f32(const float* q, const float* qd, const float* u, float gravity, int64_t B, float* out, void* ws,
-                     size_t ws_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fdso_launch<float>(q, qd, u, gravity, B, out, ws, ws_bytes, stream);
-}
-#endif
-#ifdef RBD_TU_FDSO_F64
-int rbd_fdsva_so_f64(const double* q, const double* qd, const double* u, double gravity, int64_t B, double* out, void* ws,
-                     size_t ws_bytes, void* stream) {
-  RbdStreamDevice sd_(stream); return fdso_launch<double>(q, qd, u, gravity, B, out, ws, ws_bytes, stream);
-}
-#endif
-#ifdef RBD_TU_ROLL_F32
-int rbd_rollout_f32(const float* q0, const float* qd0, const float* u, int u_shared, float dt, float gravity, int integrator,
-                    int64_t B, int64_t T, float* q_out, float* qd_out, int trajectory, void* stream) {
-  RbdStreamDevice sd_(stream); return rollout_launch<float>(q0, qd0, u, u_shared, dt, gravity, integrator, B, T, q_out, qd_out, trajectory, stream);
-}
-#endif
-#ifdef RBD_TU_ROLL_F64
-int rbd_rollout_f64(const double* q0, const double* qd0, const double* u, int u_shared, double dt, double gravity,
-                    int integrator, int64_t B, int64_t T, double* q_out, double* qd_out, int trajectory, void* stream) {
-  RbdStreamDevice sd_(stream); return rollout_launch<double>(q0, qd0, u, u_shared, dt, gravity, integrator, B, T, q_out, qd_out, trajectory, stream);
-}
-#endif
-#ifdef RBD_TU_EE_F64
-int rbd_ee_pose_f64(const double* q, int64_t B, const int32_t* site_body, const double* site_T, const double* offset, int n_sites,
-                    double* pose, double* dpose, void* stream) {
-  RbdStreamDevice sd_(stream); return ee_launch<double>(q, B, site_body, site_T, offset, n_sites, pose, dpose, stream);
-}
-#endif
-
-// ---- stubs (-DRBD_TU_STUBS with -DRBD_STUB_<unit> per missing unit): a FAMILY library holds COMMON, the units of one
-// family and these, so that it links and loads like a full library; an entry point of another family says so ------
-#ifdef RBD_TU_STUBS
-#define RBD_STUB_BODY(name) { return fail(RBD_ERR_NOT_BUILT, name ": not part of this family library (rbdreference_amd.build: first-use build)"); }
-#define RBD_STUBS_RNEA(SFX, T)                                                                                                   \
-  int rbd_rnea_kernel_name_##SFX(int64_t, char*, size_t) RBD_STUB_BODY("rbd_kernel_name(RBD_OP_RNEA)")                           \
-  int rbd_rnea_##SFX(const T*, const T*, const T*, T, int64_t, T*, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea")                  \
-  int rbd_rnea_fpass_##SFX(const T*, const T*, const T*, T, int64_t, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_fpass")          \
-  int rbd_rnea_bpass_##SFX(const T*, T*, int64_t, T*, void*) RBD_STUB_BODY("rbd_rnea_bpass")
-#define RBD_STUBS_GRAD(SFX, T)                                                                                                   \
-  int rbd_grad_kernel_name_##SFX(int64_t, char*, size_t) RBD_STUB_BODY("rbd_kernel_name(RBD_OP_RNEA_GRAD)")                      \
-  int rbd_rnea_grad_##SFX(const T*, const T*, const T*, T, int, int64_t, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_grad")           \
-  int rbd_rnea_with_grad_##SFX(const T*, const T*, const T*, T, int, int64_t, T*, T*, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_with_grad")
-#define RBD_STUBS_GRADN(SFX, T)                                                                                                  \
-  int rbd_grad_noqdd_##SFX(const T*, const T*, T, int, int64_t, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_grad (qdd = NULL)")      \
-  int rbd_grad_cols_noqdd_##SFX(const T*, const T*, T, int, int64_t, T*, T*, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_with_grad (qdd = NULL)")
-#define RBD_STUBS_MINV(SFX, T)                                                                                                   \
-  int rbd_minv_kernel_name_##SFX(int64_t, char*, size_t) RBD_STUB_BODY("rbd_kernel_name(RBD_OP_MINV)")                           \
-  int rbd_minv_needs_ws_##SFX(void) { return 1; }                                                                                \
-  int rbd_crba_##SFX(const T*, int64_t, T*, void*) RBD_STUB_BODY("rbd_crba")                                                     \
-  int rbd_minv_##SFX(const T*, int64_t, int, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_minv")                                 \
-  int rbd_minv_fd_##SFX(const T*, int64_t, T*, void*, size_t, void*, const T*, const T*, T*, const T*, T) RBD_STUB_BODY("rbd_minv")
-#define RBD_STUBS_FD(SFX, T)                                                                                                     \
-  int rbd_aba_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) RBD_STUB_BODY("rbd_aba")                                \
-  int rbd_forward_dynamics_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_forward_dynamics") \
-  int rbd_forward_dynamics_grad_##SFX(const T*, const T*, const T*, T, int64_t, T*, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_forward_dynamics_grad")
-#define RBD_STUBS_PASS(SFX, T)                                                                                                   \
-  int rbd_rnea_grad_fpass_dq_##SFX(const T*, const T*, const T*, const T*, T, int64_t, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_grad_fpass_dq") \
-  int rbd_rnea_grad_fpass_dqd_##SFX(const T*, const T*, const T*, int64_t, T*, T*, T*, void*) RBD_STUB_BODY("rbd_rnea_grad_fpass_dqd") \
-  int rbd_rnea_grad_bpass_dq_##SFX(const T*, const T*, T*, int64_t, T*, void*) RBD_STUB_BODY("rbd_rnea_grad_bpass_dq")           \
-  int rbd_rnea_grad_bpass_dqd_##SFX(const T*, T*, int, int64_t, T*, void*) RBD_STUB_BODY("rbd_rnea_grad_bpass_dqd")              \
-  int rbd_minv_bpass_##SFX(const T*, int64_t, T*, T*, T*, T*, void*) RBD_STUB_BODY("rbd_minv_bpass")                             \
-  int rbd_minv_fpass_##SFX(const T*, int64_t, T*, T*, const T*, const T*, void*) RBD_STUB_BODY("rbd_minv_fpass")
-#define RBD_STUBS_EE(SFX, T)                                                                                                     \
-  int rbd_ee_pose_##SFX(const T*, int64_t, const int32_t*, const double*, const double*, int, T*, T*, void*) RBD_STUB_BODY("rbd_ee_pose")
-#define RBD_STUBS_SO(SFX, T)                                                                                                     \
-  int rbd_second_order_idsva_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) RBD_STUB_BODY("rbd_second_order_idsva")
-#define RBD_STUBS_FDSO(SFX, T)                                                                                                   \
-  int rbd_fdsva_so_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_fdsva_so")
-#define RBD_STUBS_ROLL(SFX, T)                                                                                                   \
-  int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) RBD_STUB_BODY("rbd_rollout")
-#ifdef RBD_STUB_ROLL_F32
-RBD_STUBS_ROLL(f32, float)
-#endif
-#ifdef RBD_STUB_ROLL_F64
-RBD_STUBS_ROLL(f64, double)
-#endif
-#ifdef RBD_STUB_FDSO_F32
-RBD_STUBS_FDSO(f32, float)
-#endif
-#ifdef RBD_STUB_FDSO_F64
-RBD_STUBS_FDSO(f64, double)
-#endif
-#ifdef RBD_STUB_SO_F32
-RBD_STUBS_SO(f32, float)
-#endif
-#ifdef RBD_STUB_SO_F64
-RBD_STUBS_SO(f64, double)
-#endif
-#ifdef RBD_STUB_EE_F32
-RBD_STUBS_EE(f32, float)
-#endif
-#ifdef RBD_STUB_EE_F64
-RBD_STUBS_EE(f64, double)
-#endif
-#ifdef RBD_STUB_RNEA_F32
-RBD_STUBS_RNEA(f32, float)
-#endif
-#ifdef RBD_STUB_RNEA_F64
-RBD_STUBS_RNEA(f64, double)
-#endif
-#ifdef RBD_STUB_GRAD_F32
-RBD_STUBS_GRAD(f32, float)
-#endif
-#ifdef RBD_STUB_GRAD_F64
-RBD_STUBS_GRAD(f64, double)
-#endif
-#ifdef RBD_STUB_GRADN_F32
-RBD_STUBS_GRADN(f32, float)
-#endif
-#ifdef RBD_STUB_GRADN_F64
-RBD_STUBS_GRADN(f64, double)
-#endif
-#ifdef RBD_STUB_MINV_F32
-RBD_STUBS_MINV(f32, float)
-#endif
-#ifdef RBD_STUB_MINV_F64
-RBD_STUBS_MINV(f64, double)
-#endif
-#ifdef RBD_STUB_FD_F32
-RBD_STUBS_FD(f32, float)
-#endif
-#ifdef RBD_STUB_FD_F64
-RBD_STUBS_FD(f64, double)
-#endif
-#ifdef RBD_STUB_PASS_F32
-RBD_STUBS_PASS(f32, float)
-#endif
-#ifdef RBD_STUB_PASS_F64
-RBD_STUBS_PASS(f64, double)
-#endif
-#endif  // RBD_TU_STUBS
-
-}  // extern "C"
+// The host half -- kernel selection, launchers and the C-ABI of include/rbd_hip.h -- is rbd_capi.h, over the shared launch
+// path of rbd_host.h; the workspace pool of the COMMON unit is rbd_ws_pool.h.
+#include "rbd_capi.h"
