@@ -341,6 +341,51 @@ int rbd_rollout_f32(const float* q0, const float* qd0, const float* u, int u_sha
 int rbd_rollout_f64(const double* q0, const double* qd0, const double* u, int u_shared, double dt, double gravity,
                     int integrator, int64_t B, int64_t T, double* q_out, double* qd_out, int trajectory, void* stream);
 
+/* Reverse-mode gradient of a rollout: for a scalar L of the returned slices, dL/du [T, B, n], dL/dq0 and dL/dqd0 [B, n]
+ * from gq[t] = dL/dq[t] and gqd[t] = dL/dqd[t] (the direct partials; slice t is the state after step t + 1).  Fixed base
+ * only; a floating-base library returns RBD_ERR_UNSUPPORTED.  With lam = (lq | lqd) = 0, for t = T-1 ... 0, at the
+ * linearisation point (q_t, qd_t, u_t) -- (q0, qd0, u[0]) for t = 0, (q[t-1], qd[t-1], u[t]) after it:
+ *   lq += gq[t];  lqd += gqd[t];  w = lqd + dt lq
+ *   mu = dt w (integrator 0)  |  dt lqd (integrator 1);   nu = Minv(q_t) mu;   grad_u[t] = nu
+ *   lq = lq - dc_dq^T nu;  lqd = w - dc_dqd^T nu     [dc_dq | dc_dqd] = rnea_grad at (q_t, qd_t, qdd_t), qdd_t = aba at (q_t, qd_t, u_t)
+ * and grad_q0 = lq, grad_qd0 = lqd after t = 0.  Only vector-Jacobian products are formed: no -Minv dc_du.
+ * PRISMATIC JOINTS: rbd_rnea_grad's dc_dq reproduces the reference and is not the q-derivative for prismatic joints,
+ * and these gradients inherit that: they are the true gradient on robots with revolute joints only.
+ *
+ * rbd_rollout_adjoint: the scan alone, ONE launch that walks the time axis with lam on chip, for a caller that holds the
+ * linearisation.  Per row and step it reads n 2n + n n + 2n scalars and writes n.
+ *   dc_du [T, B, n, 2n], Minv [T, B, n, n] (dense, symmetric): step t's linearisation; T here is the number of steps
+ *                 of THIS call
+ *   gq, gqd     : g_final_only == 0: [T, B, n]; g_final_only != 0: [B, n], added at step T - 1 only (a terminal cost;
+ *                 a caller that splits the time axis passes them to the call that holds the last step).  Either may be
+ *                 NULL = zero
+ *   lam         : [B, 2n], IN and OUT: the adjoint after step T (zeros at the end of the horizon) -> the adjoint after
+ *                 step 0.  It is loaded and stored as it is, so a scan split at any step -- the later steps first, lam
+ *                 carried through this buffer -- is bit-identical to the unsplit one
+ *   grad_u      : [T, B, n]
+ * rbd_rollout_grad: the composite.  q_traj, qd_traj [T, B, n] are rbd_rollout's trajectory (slice T - 1 is not read);
+ * it zeroes lam and walks chunks of Tc steps from the end: rbd_aba, rbd_rnea_grad without damping and rbd_minv on the
+ * chunk's Tc B flat rows (time-major: rows of steps 1 .. T-1 are contiguous in q_traj and u), then the scan; step 0 is
+ * its own last chunk.  Tc is the largest chunk (at most T - 1, at least 1) whose rbd_rollout_grad_workspace_bytes(B, Tc,
+ * elem_size) fits ws_bytes; rbd_rollout_grad_workspace_bytes(B, T, .) therefore always suffices.  The result does not
+ * depend on Tc beyond the kernels rbd_rnea_grad / rbd_minv pick for a batch of Tc B rows.
+ * Arguments are checked before anything touches the GPU: null required pointer, B < 0, T < 0, dt not finite, unknown
+ * integrator, B T n 2n too large, misaligned lam / grad_u / grad_q0 / grad_qd0 / workspace: RBD_ERR_ARG; a workspace
+ * that does not hold one step: RBD_ERR_WORKSPACE.  B == 0 or T == 0 is a no-op: nothing is written. */
+int rbd_rollout_adjoint_f32(const float* dc_du, const float* Minv, const float* gq, const float* gqd, int g_final_only,
+                            float dt, int integrator, int64_t B, int64_t T, float* lam, float* grad_u, void* stream);
+int rbd_rollout_adjoint_f64(const double* dc_du, const double* Minv, const double* gq, const double* gqd, int g_final_only,
+                            double dt, int integrator, int64_t B, int64_t T, double* lam, double* grad_u, void* stream);
+size_t rbd_rollout_grad_workspace_bytes(int64_t B, int64_t Tc, int elem_size);
+int rbd_rollout_grad_f32(const float* q0, const float* qd0, const float* u, const float* q_traj, const float* qd_traj,
+                         const float* gq, const float* gqd, int g_final_only, float dt, float gravity, int integrator,
+                         int64_t B, int64_t T, float* grad_u, float* grad_q0, float* grad_qd0, void* ws, size_t ws_bytes,
+                         void* stream);
+int rbd_rollout_grad_f64(const double* q0, const double* qd0, const double* u, const double* q_traj, const double* qd_traj,
+                         const double* gq, const double* gqd, int g_final_only, double dt, double gravity, int integrator,
+                         int64_t B, int64_t T, double* grad_u, double* grad_q0, double* grad_qd0, void* ws, size_t ws_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = [
     "rbd_second_order_idsva_f32", "rbd_second_order_idsva_f64",
     "rbd_fdsva_so_workspace_bytes", "rbd_fdsva_so_f32", "rbd_fdsva_so_f64",
     "rbd_rollout_f32", "rbd_rollout_f64",
+    "rbd_rollout_adjoint_f32", "rbd_rollout_adjoint_f64",
+    "rbd_rollout_grad_workspace_bytes", "rbd_rollout_grad_f32", "rbd_rollout_grad_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -132,6 +134,15 @@ def _declare(lib):
         f = getattr(lib, f"rbd_rollout_{sfx}")
         f.restype = c_int
         f.argtypes = [c_void_p, c_void_p, c_void_p, c_int, ct, ct, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]
+        f = getattr(lib, f"rbd_rollout_adjoint_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ct, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
+        f = getattr(lib, f"rbd_rollout_grad_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ct, ct, c_int, c_int64, c_int64,
+                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.rbd_rollout_grad_workspace_bytes.restype = c_size_t
+    lib.rbd_rollout_grad_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_fdsva_so_workspace_bytes.restype = c_size_t
     lib.rbd_fdsva_so_workspace_bytes.argtypes = [c_int64, c_int]
     lib.rbd_minv_workspace_bytes.restype = c_size_t

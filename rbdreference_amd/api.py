@@ -110,6 +110,35 @@ class BoundLaunch:
         return self.outputs
 
 
+def _rollout_function():
+    """The ``torch.autograd.Function`` behind ``rollout(..., differentiable=True)`` (made on first use)."""
+    global _RolloutFunction
+    if _RolloutFunction is None:
+        from torch.autograd.function import once_differentiable
+
+        class RolloutFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, q0, qd0, u, rbd, dt, gravity, integrator, trajectory):
+                q, qd = rbd.rollout(q0.detach(), qd0.detach(), u.detach(), dt, gravity, integrator, True)
+                ctx.save_for_backward(q0, qd0, u, q, qd)
+                ctx.args = (rbd, dt, gravity, integrator, trajectory)
+                return (q, qd) if trajectory else (q[-1].clone(), qd[-1].clone())
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, gq, gqd):
+                q0, qd0, u, q, qd = ctx.saved_tensors
+                rbd, dt, gravity, integrator, trajectory = ctx.args
+                gu, gq0, gqd0 = rbd.rollout_grad(q0, qd0, u, dt, gq, gqd, gravity, integrator, q=q, qd=qd)
+                return gq0, gqd0, gu, None, None, None, None, None
+
+        _RolloutFunction = RolloutFunction
+    return _RolloutFunction.apply
+
+
+_RolloutFunction = None
+
+
 class RBDReference:
     def __init__(self, robotObj, build: bool = True, generic=None):
         """``generic`` ('auto' | 'only' | 'never', default ``RBD_GENERIC`` or 'auto'): whether the model-handle library
@@ -842,7 +871,7 @@ class RBDReference:
         return out[..., 0, :, :, :], out[..., 1, :, :, :], out[..., 2, :, :, :], out[..., 3, :, :, :]
 
     # ---- forward-simulation rollouts: rbd_rollout, T steps of aba + integrator in one launch -------------------------
-    def rollout(self, q0, qd0, u, dt, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True):
+    def rollout(self, q0, qd0, u, dt, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True, differentiable=False):
         """Integrate ``qdd_t = aba(q_t, qd_t, u_t, GRAVITY)`` over ``T`` steps of size ``dt`` in ONE kernel launch (the
         state stays on chip between steps) -> ``(q, qd)``.  Not part of the reference: a sampling controller's loop.
 
@@ -855,12 +884,21 @@ class RBDReference:
         initial state is not copied), a contiguous ``[B, n]`` tensor that ``rnea_grad``, ``forward_dynamics_grad`` or
         ``fdsva_so`` take as it is.  ``trajectory=False`` returns the final state ``[B, n]`` only and writes nothing
         else.  ``q0 [n]`` with ``u [T, n]`` gives ``[T, n]`` (``[n]``).  numpy in -> float64 numpy out; tensors stay on
-        their device and dtype and run on torch's current stream."""
+        their device and dtype and run on torch's current stream.
+
+        ``differentiable=True`` (tensors only): the result comes from a ``torch.autograd.Function`` whose backward is
+        ``rollout_grad`` on the saved trajectory (once differentiable), so ``loss(q, qd).backward()`` fills ``q0.grad``,
+        ``qd0.grad`` and ``u.grad``.  With ``trajectory=False`` the trajectory is still computed and kept for the
+        backward pass; the last slice is returned."""
         from ._lib import RBD_INTEGRATORS
         if self.model.floating:
             raise NotImplementedError("rollout: fixed-base robots only (a floating base needs an integrator on SE(3))")
         if integrator not in RBD_INTEGRATORS:
             raise ValueError(f"rollout: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        if differentiable:
+            if not all(isinstance(x, torch.Tensor) for x in (q0, qd0, u)):
+                raise TypeError("rollout: differentiable=True takes torch tensors (autograd does not see numpy arrays)")
+            return _rollout_function()(q0, qd0, u, self, float(dt), float(GRAVITY), integrator, bool(trajectory))
         n = self.n
         sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
         if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
@@ -897,6 +935,174 @@ class RBDReference:
         if unb:
             q, qd = q.squeeze(-2), qd.squeeze(-2)
         return (q.cpu().numpy(), qd.cpu().numpy()) if is_np else (q, qd)
+
+    # ---- reverse-mode gradient of a rollout: rbd_rollout_grad (aba, rnea_grad, minv per chunk + one scan launch) ------
+    _ROLLG_WS_CAP = 1 << 30
+
+    @staticmethod
+    def _rollg_g_shape(gq, gqd, T, B, n, unb, who):
+        """Shape check of the two cost gradients, before anything touches the GPU -> g_final_only."""
+        if gq is None and gqd is None:
+            raise ValueError(f"{who}: give grad_q, grad_qd or both (the gradient of the cost with respect to the trajectory)")
+        full, fin = ((T, n), (n,)) if unb else ((T, B, n), (B, n))
+        shapes = [tuple(np.shape(g)) for g in (gq, gqd) if g is not None]
+        if any(sh not in (full, fin) for sh in shapes) or len(set(shapes)) != 1:
+            raise ValueError(f"{who}: grad_q and grad_qd must both be {list(full)} or both {list(fin)} (final state), got {shapes}")
+        return shapes[0] == fin
+
+    def rollout_grad(self, q0, qd0, u, dt, grad_q=None, grad_qd=None, GRAVITY=-9.81, integrator="semi_implicit",
+                     q=None, qd=None, workspace_bytes=None):
+        """Reverse-mode gradient of ``rollout``: for a scalar cost ``L`` of the returned slices, with
+        ``grad_q[t] = dL/dq[t]`` and ``grad_qd[t] = dL/dqd[t]`` (the direct partials), ->
+        ``(grad_u, grad_q0, grad_qd0) = (dL/du, dL/dq0, dL/dqd0)``.  Not part of the reference.
+
+        The backward recursion over time runs as one HIP launch per chunk of the horizon with the adjoint on chip
+        (``rbd_rollout_adj.h``), after ``aba``, ``rnea_grad`` and ``minv`` on the chunk's flat rows; it forms
+        vector-Jacobian products only, never ``forward_dynamics_grad``'s ``-Minv dc_du``.
+
+        Conventions are ``rollout``'s: time-major, ``q0, qd0 [B, n]``, ``u [T, B, n]`` -> ``grad_u [T, B, n]``; a shared
+        ``u [T, n]`` is expanded and ``grad_u`` summed over ``B`` to ``[T, n]``; ``q0 [n]`` with ``u [T, n]`` is one row.
+        ``grad_q, grad_qd``: ``[T, B, n]``, or ``[B, n]`` = the gradient with respect to the final state alone (a
+        terminal cost); at least one must be given, both in the same form.  ``q, qd``: the trajectory ``rollout``
+        returned for these inputs (``[T, B, n]``); computed here when omitted.  ``workspace_bytes``: device scratch for
+        the linearisation, which decides how many steps one chunk holds (default: all of them, capped at 1 GiB).
+        numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
+
+        Robots with PRISMATIC joints: ``rnea_grad``'s ``dc_dq`` reproduces the reference and is not the q-derivative for
+        such joints (see ``fdsva_so``), and this gradient inherits that: it is the true gradient on robots with
+        revolute joints only.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        if self.model.floating:
+            raise NotImplementedError("rollout_grad: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"rollout_grad: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
+        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"rollout_grad: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        unb = len(sq) == 1
+        B = 1 if unb else sq[0]
+        shared = len(su) == 2
+        if unb and not shared:
+            raise ValueError(f"rollout_grad: q0 [{n}] takes u [T, {n}], got {su}")
+        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
+            raise ValueError(f"rollout_grad: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
+        T = su[0]
+        if T == 0:
+            raise ValueError("rollout_grad: u holds no step (T == 0)")
+        final = self._rollg_g_shape(grad_q, grad_qd, T, B, n, unb, "rollout_grad")
+        if (q is None) != (qd is None):
+            raise ValueError("rollout_grad: give both q and qd (the trajectory of rollout) or neither")
+        traj = (T, n) if unb else (T, B, n)
+        if q is not None and (tuple(np.shape(q)) != traj or tuple(np.shape(qd)) != traj):
+            raise ValueError(f"rollout_grad: q and qd must be the trajectory {list(traj)}, got {tuple(np.shape(q))} and {tuple(np.shape(qd))}")
+        if workspace_bytes is not None and int(workspace_bytes) < 0:
+            raise ValueError("rollout_grad: workspace_bytes < 0")
+        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
+
+        def dev_tensor(x):
+            if isinstance(x, torch.Tensor):
+                if is_np:
+                    raise TypeError("mixing numpy and torch inputs is not supported")
+                if x.device != dev or x.dtype != dtp:
+                    raise TypeError("all inputs must share device and dtype")
+                return x.contiguous()
+            if not is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).contiguous()
+        u = dev_tensor(u)
+        gq = None if grad_q is None else dev_tensor(grad_q)
+        gqd = None if grad_qd is None else dev_tensor(grad_qd)
+        if q is not None:
+            q, qd = dev_tensor(q), dev_tensor(qd)
+        esz = 4 if dtp == torch.float32 else 8
+        sfx = "f32" if esz == 4 else "f64"
+        with torch.cuda.device(dev):
+            if shared:
+                u = u[:, None, :].expand(T, B, n).contiguous()
+            if q is None:
+                q, qd = self.rollout(q0, qd0, u, dt, GRAVITY, integrator)
+            gu = torch.empty((T, B, n), device=dev, dtype=dtp)
+            gq0 = torch.empty((B, n), device=dev, dtype=dtp)
+            gqd0 = torch.empty((B, n), device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib = self._lib.resolve("rbd_rollout_grad", sfx)    # ONE resolution: workspace size and entry point from the same library
+            if workspace_bytes is None:
+                wsb = int(lib.rbd_rollout_grad_workspace_bytes(B, T, esz))
+                wsb = max(min(wsb, self._ROLLG_WS_CAP), int(lib.rbd_rollout_grad_workspace_bytes(B, 1, esz)))
+            else:
+                wsb = int(workspace_bytes)
+            ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
+            self._lib.check(getattr(lib, f"rbd_rollout_grad_{sfx}")(
+                self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(q), self._ptr(qd), self._ptr(gq), self._ptr(gqd), int(final),
+                float(dt), float(GRAVITY), RBD_INTEGRATORS[integrator], B, T, self._ptr(gu), self._ptr(gq0), self._ptr(gqd0),
+                ws.data_ptr(), wsb, st))
+            if shared:
+                gu = gu.sum(1)
+        if unb:
+            gq0, gqd0 = gq0[0], gqd0[0]
+        return tuple(x.cpu().numpy() for x in (gu, gq0, gqd0)) if is_np else (gu, gq0, gqd0)
+
+    def rollout_adjoint(self, dc_du, Minv, dt, grad_q=None, grad_qd=None, integrator="semi_implicit", lam=None):
+        """The scan of ``rollout_grad`` alone (``rbd_rollout_adjoint``), for a caller who holds the linearisation:
+        ``dc_du [T, B, n, 2n]`` (``rnea_grad``) and ``Minv [T, B, n, n]`` (dense) of the ``T`` steps, time-major ->
+        ``(grad_u [T, B, n], lam [B, 2n])``.  ``lam = (lq | lqd)`` is the adjoint entering at the END of these steps
+        (default zeros) and is returned as it leaves at their beginning -- ``(dL/dq0 | dL/dqd0)`` when they start the
+        horizon; a contiguous tensor is updated in place.  A horizon may be split: the later steps first, ``lam`` carried
+        over, bit-identical to one call.  ``grad_q, grad_qd``: ``[T, B, n]``, or ``[B, n]`` for the last of these steps
+        alone.  numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
+        The prismatic-joint caveat of ``rollout_grad`` applies.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        if self.model.floating:
+            raise NotImplementedError("rollout_adjoint: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"rollout_adjoint: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sd, sm = tuple(np.shape(dc_du)), tuple(np.shape(Minv))
+        if len(sd) != 4 or sd[2:] != (n, 2 * n) or sm != sd[:2] + (n, n):
+            raise ValueError(f"rollout_adjoint: dc_du must be [T, B, {n}, {2 * n}] and Minv [T, B, {n}, {n}], got {sd} and {sm}")
+        T, B = sd[:2]
+        if T == 0:
+            raise ValueError("rollout_adjoint: no step (T == 0)")
+        final = self._rollg_g_shape(grad_q, grad_qd, T, B, n, False, "rollout_adjoint")
+        if lam is not None and tuple(np.shape(lam)) != (B, 2 * n):
+            raise ValueError(f"rollout_adjoint: lam must be [{B}, {2 * n}], got {tuple(np.shape(lam))}")
+        is_np = not isinstance(dc_du, torch.Tensor)
+        if is_np:
+            if not torch.cuda.is_available():
+                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
+            dev, dtp = torch.device("cuda", 0), torch.float64
+        else:
+            dev, dtp = dc_du.device, dc_du.dtype
+            if dev.type != "cuda":
+                raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
+            if dtp not in (torch.float32, torch.float64):
+                raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
+
+        def dev_tensor(x):
+            if x is None:
+                return None
+            if isinstance(x, torch.Tensor):
+                if is_np:
+                    raise TypeError("mixing numpy and torch inputs is not supported")
+                if x.device != dev or x.dtype != dtp:
+                    raise TypeError("all inputs must share device and dtype")
+                return x.contiguous()
+            if not is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).contiguous()
+        dc_du, Minv, gq, gqd = (dev_tensor(x) for x in (dc_du, Minv, grad_q, grad_qd))
+        with torch.cuda.device(dev):
+            if lam is None:
+                lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp)
+            else:
+                lam_t = dev_tensor(lam)
+            gu = torch.empty((T, B, n), device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_rollout_adjoint", dtp)(
+                self._ptr(dc_du), self._ptr(Minv), self._ptr(gq), self._ptr(gqd), int(final), float(dt),
+                RBD_INTEGRATORS[integrator], B, T, self._ptr(lam_t), self._ptr(gu), st))
+        return (gu.cpu().numpy(), lam_t.cpu().numpy()) if is_np else (gu, lam_t)
 
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):

@@ -683,6 +683,130 @@ int rollout_launch(const T* q0, const T* qd0, const T* u, int u_shared, T dt, T 
 }
 #endif  // RBD_NEED_ROLL
 
+// rbd_rollout_grad's workspace for chunks of Tc steps, R = Tc B flat rows: minv's scratch | qdd [R, N] | dc_du [R, N, 2N] |
+// Minv [R, N, N] | lam [B, 2N]
+#if defined(RBD_TU_COMMON) || defined(RBD_NEED_ROLLG)
+constexpr int64_t ROLLG_MAX_ROWS = (int64_t)1 << 30;      // rows of one chunk, and B: every launcher's grid holds them
+template <class T>
+struct RollgWorkspace {
+  size_t minv_ws_bytes, off_qdd, off_dcdu, off_minv, off_lam, total;
+  RollgWorkspace(int64_t B, int64_t Tc) {
+    using namespace rbdk;
+    const size_t R = (size_t)B * (size_t)Tc;
+    size_t o = 0;
+    minv_ws_bytes = R * MINV_WS_PER_CFG * sizeof(T);
+    o += align16(minv_ws_bytes);
+    off_qdd = o;  o += align16(R * N * sizeof(T));
+    off_dcdu = o; o += align16(R * 2 * N * N * sizeof(T));
+    off_minv = o; o += align16(R * N * N * sizeof(T));
+    off_lam = o;  o += align16((size_t)B * 2 * N * sizeof(T));
+    total = o;
+  }
+};
+#endif
+
+#ifdef RBD_NEED_ROLLG
+// (rbd_aba of the FD unit, as the overloads of RBD_CROSS_UNIT)
+inline int rbd_aba(const float* q, const float* qd, const float* tau, float g, int64_t B, float* qdd, void* s) {
+  return rbd_aba_f32(q, qd, tau, g, B, qdd, s);
+}
+inline int rbd_aba(const double* q, const double* qd, const double* tau, double g, int64_t B, double* qdd, void* s) {
+  return rbd_aba_f64(q, qd, tau, g, B, qdd, s);
+}
+// what rbd_rollout_adjoint and rbd_rollout_grad refuse alike, before any launch
+template <class T>
+int rollg_check(const char* who, T dt, int integrator, int64_t B, int64_t steps) {
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "%s: fixed-base robots only", who);
+  if (B < 0) return fail(RBD_ERR_ARG, "%s: B < 0", who);
+  if (steps < 0) return fail(RBD_ERR_ARG, "%s: T < 0", who);
+  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "%s: dt must be finite", who);
+  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
+    return fail(RBD_ERR_ARG, "%s: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)", who);
+  return 0;
+}
+// B T n 2n elements of dc_du: byte offsets stay far inside int64
+int rollg_check_size(const char* who, int64_t B, int64_t steps) {
+  if (B > ROLLG_MAX_ROWS) return fail(RBD_ERR_ARG, "%s: B too large", who);
+  if (steps > (INT64_MAX / 64) / (B * rbdk::N * 2 * rbdk::N)) return fail(RBD_ERR_ARG, "%s: B * T * n * 2n too large", who);
+  return 0;
+}
+
+// the scan (rbd_rollout_adj.h): one launch for `steps` steps; out_q0 / out_qd0 (the composite's last chunk) may be null
+template <class T>
+int rollg_scan(const char* who, const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator,
+               int64_t B, int64_t steps, T* lam, T* grad_u, T* out_q0, T* out_qd0, void* stream) {
+  using namespace rbdk;
+  unsigned grid;
+  if (int rc = grid_for(B, rollg_cfgs(), who, &grid)) return rc;
+  return launch(who, rollout_adjoint_kernel<T>, grid, rollg_threads(), 0, stream, dc_du, Minv, gq, gqd, g_final_only ? 1 : 0, dt,
+                integrator, B, steps, lam, grad_u, out_q0, out_qd0);
+}
+
+template <class T>
+int rollout_adjoint_launch(const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator,
+                           int64_t B, int64_t steps, T* lam, T* grad_u, void* stream) {
+  if (int rc = rollg_check<T>("rbd_rollout_adjoint", dt, integrator, B, steps)) return rc;
+  if (B == 0 || steps == 0) return 0;
+  if (!dc_du || !Minv || !lam || !grad_u) return fail(RBD_ERR_ARG, "rbd_rollout_adjoint: dc_du, Minv, lam and grad_u must be non-null");
+  if (misaligned(lam, grad_u)) return fail(RBD_ERR_ARG, "rbd_rollout_adjoint: output buffers must be 16-byte aligned");
+  if (int rc = rollg_check_size("rbd_rollout_adjoint", B, steps)) return rc;
+  return rollg_scan<T>("rbd_rollout_adjoint launch", dc_du, Minv, gq, gqd, g_final_only, dt, integrator, B, steps, lam, grad_u,
+                       nullptr, nullptr, stream);
+}
+
+// rbd_rollout_grad: lam = 0, then chunks of the time axis from the end -- aba, rnea_grad, minv on the chunk's flat rows (the
+// existing entry points, on the caller's stream), then the scan.  Step 0 is linearised at (q0, qd0, u[0]): its own chunk.
+template <class T>
+int rollout_grad_launch(const T* q0, const T* qd0, const T* u, const T* q_traj, const T* qd_traj, const T* gq, const T* gqd,
+                        int g_final_only, T dt, T gravity, int integrator, int64_t B, int64_t steps, T* grad_u, T* grad_q0,
+                        T* grad_qd0, void* workspace, size_t wsb, void* stream) {
+  using namespace rbdk;
+  if (int rc = rollg_check<T>("rbd_rollout_grad", dt, integrator, B, steps)) return rc;
+  if (B == 0 || steps == 0) return 0;
+  if (!q0 || !qd0 || !u || !q_traj || !qd_traj || !grad_u || !grad_q0 || !grad_qd0)
+    return fail(RBD_ERR_ARG, "rbd_rollout_grad: q0, qd0, u, q_traj, qd_traj, grad_u, grad_q0 and grad_qd0 must be non-null");
+  if (misaligned(grad_u, grad_q0, grad_qd0)) return fail(RBD_ERR_ARG, "rbd_rollout_grad: output buffers must be 16-byte aligned");
+  if (int rc = rollg_check_size("rbd_rollout_grad", B, steps)) return rc;
+  if (!workspace || wsb < RollgWorkspace<T>(B, 1).total)
+    return fail(RBD_ERR_WORKSPACE, "rbd_rollout_grad: workspace missing or smaller than rbd_rollout_grad_workspace_bytes(B, 1, .)");
+  if (misaligned(workspace)) return fail(RBD_ERR_ARG, "rbd_rollout_grad: workspace must be 16-byte aligned");
+  // the largest chunk that fits (the size grows with Tc)
+  int64_t Tc = 1, hi_tc = steps - 1 < ROLLG_MAX_ROWS / B ? steps - 1 : ROLLG_MAX_ROWS / B;
+  while (Tc < hi_tc) {
+    const int64_t mid = Tc + (hi_tc - Tc + 1) / 2;
+    if (RollgWorkspace<T>(B, mid).total <= wsb) Tc = mid; else hi_tc = mid - 1;
+  }
+  const RollgWorkspace<T> L(B, Tc);
+  char* w = reinterpret_cast<char*>(workspace);
+  T* qdd = reinterpret_cast<T*>(w + L.off_qdd);
+  T* dc = reinterpret_cast<T*>(w + L.off_dcdu);
+  T* Mi = reinterpret_cast<T*>(w + L.off_minv);
+  T* lam = reinterpret_cast<T*>(w + L.off_lam);
+  const hipError_t e = hipMemsetAsync(lam, 0, (size_t)B * 2 * N * sizeof(T), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "rbd_rollout_grad (zeroing the adjoint)");
+  const int64_t row = B * N;
+  // steps [lo, hi) at rows q, qd, uu; g is dense [T, B, N] or belongs to step T - 1 alone
+  auto chunk = [&](const T* q, const T* qd, int64_t lo, int64_t hi) {
+    const int64_t R = (hi - lo) * B;
+    const bool last = hi == steps;
+    const T* cgq = g_final_only ? (last ? gq : nullptr) : (gq ? gq + lo * row : nullptr);
+    const T* cgqd = g_final_only ? (last ? gqd : nullptr) : (gqd ? gqd + lo * row : nullptr);
+    int rc;
+    if ((rc = rbd_aba(q, qd, u + lo * row, gravity, R, qdd, stream)) != 0) return rc;
+    if ((rc = rbd_rnea_grad(q, qd, qdd, gravity, 0, R, nullptr, dc, stream)) != 0) return rc;
+    if ((rc = rbd_minv(q, R, 1, Mi, w, L.minv_ws_bytes, stream)) != 0) return rc;
+    return rollg_scan<T>("rbd_rollout_grad (scan) launch", dc, Mi, cgq, cgqd, g_final_only, dt, integrator, B, hi - lo, lam,
+                         grad_u + lo * row, lo == 0 ? grad_q0 : nullptr, lo == 0 ? grad_qd0 : nullptr, stream);
+  };
+  for (int64_t hi = steps; hi > 1;) {
+    const int64_t lo = hi - Tc > 1 ? hi - Tc : 1;
+    if (int rc = chunk(q_traj + (lo - 1) * row, qd_traj + (lo - 1) * row, lo, hi)) return rc;
+    hi = lo;
+  }
+  return chunk(q0, qd0, 0, 1);
+}
+#endif  // RBD_NEED_ROLLG
+
 #ifdef RBD_NEED_EE
 // rbd_ee_pose: site table (host arrays) -> EeSites kernel argument; one launch for pose, gradient or both
 template <class T>
@@ -928,6 +1052,23 @@ RBD_DECLS_SELECTION(f64)
 #define RBD_STUBS_ROLL(SFX, T)                                                                                                   \
   int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) RBD_STUB_BODY("rbd_rollout")
 
+#define RBD_DEFS_ROLLG(SFX, T)                                                                                                   \
+  int rbd_rollout_adjoint_##SFX(const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator, \
+                                int64_t B, int64_t steps, T* lam, T* grad_u, void* stream) {                                     \
+    RBD_ENTER rollout_adjoint_launch<T>(dc_du, Minv, gq, gqd, g_final_only, dt, integrator, B, steps, lam, grad_u, stream);      \
+  }                                                                                                                              \
+  int rbd_rollout_grad_##SFX(const T* q0, const T* qd0, const T* u, const T* q_traj, const T* qd_traj, const T* gq,              \
+                             const T* gqd, int g_final_only, T dt, T gravity, int integrator, int64_t B, int64_t steps,          \
+                             T* grad_u, T* grad_q0, T* grad_qd0, void* ws, size_t ws_bytes, void* stream) {                      \
+    RBD_ENTER rollout_grad_launch<T>(q0, qd0, u, q_traj, qd_traj, gq, gqd, g_final_only, dt, gravity, integrator, B, steps,      \
+                                     grad_u, grad_q0, grad_qd0, ws, ws_bytes, stream);                                           \
+  }
+#define RBD_STUBS_ROLLG(SFX, T)                                                                                                  \
+  int rbd_rollout_adjoint_##SFX(const T*, const T*, const T*, const T*, int, T, int, int64_t, int64_t, T*, T*, void*)            \
+      RBD_STUB_BODY("rbd_rollout_adjoint")                                                                                       \
+  int rbd_rollout_grad_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, T, T, int, int64_t,      \
+                             int64_t, T*, T*, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_rollout_grad")
+
 #if defined(RBD_TU_RNEA_F32)
 RBD_DEFS_RNEA(f32, float)
 #elif defined(RBD_STUB_RNEA_F32)
@@ -1029,6 +1170,17 @@ RBD_DEFS_ROLL(f64, double)
 RBD_STUBS_ROLL(f64, double)
 #endif
 
+#if defined(RBD_TU_ROLLG_F32)
+RBD_DEFS_ROLLG(f32, float)
+#elif defined(RBD_STUB_ROLLG_F32)
+RBD_STUBS_ROLLG(f32, float)
+#endif
+#if defined(RBD_TU_ROLLG_F64)
+RBD_DEFS_ROLLG(f64, double)
+#elif defined(RBD_STUB_ROLLG_F64)
+RBD_STUBS_ROLLG(f64, double)
+#endif
+
 #ifdef RBD_TU_COMMON
 int rbd_abi_version(void) { return RBD_ABI_VERSION; }
 const char* rbd_last_error(void) { return rbd_err_buf(); }
@@ -1099,6 +1251,12 @@ size_t rbd_fdsva_so_workspace_bytes(int64_t B, int elem_size) {
   if (B <= 0 || rbdm::FLOATING_BASE || B > fdso_max_batch()) return 0;
   if (elem_size == 4) return FdsoWorkspace<float>(B).total;
   if (elem_size == 8) return FdsoWorkspace<double>(B).total;
+  return 0;
+}
+size_t rbd_rollout_grad_workspace_bytes(int64_t B, int64_t Tc, int elem_size) {
+  if (B <= 0 || Tc <= 0 || rbdm::FLOATING_BASE || B > ROLLG_MAX_ROWS || Tc > ROLLG_MAX_ROWS / B) return 0;
+  if (elem_size == 4) return RollgWorkspace<float>(B, Tc).total;
+  if (elem_size == 8) return RollgWorkspace<double>(B, Tc).total;
   return 0;
 }
 #endif  // RBD_TU_COMMON

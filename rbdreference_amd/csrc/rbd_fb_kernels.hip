@@ -364,6 +364,13 @@ RBD_DECLS_SELECTION(f64)
   int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) {              \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: fixed-base robots only (a floating base needs an integrator on SE(3))"); \
   }                                                                                                                         \
+  int rbd_rollout_adjoint_##SFX(const T*, const T*, const T*, const T*, int, T, int, int64_t, int64_t, T*, T*, void*) {    \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_adjoint: fixed-base robots only (rbd_rollout has no floating base)");    \
+  }                                                                                                                         \
+  int rbd_rollout_grad_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, T, T, int, int64_t, \
+                             int64_t, T*, T*, T*, void*, size_t, void*) {                                                   \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_grad: fixed-base robots only (rbd_rollout has no floating base)");       \
+  }                                                                                                                         \
   int rbd_aba_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) { return unsupported("rbd_aba"); }                 \
   int rbd_forward_dynamics_grad_##SFX(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, void* ws, \
                                       size_t wsb, void* stream) {                                                           \
