@@ -386,6 +386,66 @@ int rbd_rollout_grad_f64(const double* q0, const double* qd0, const double* u, c
                          int64_t B, int64_t T, double* grad_u, double* grad_q0, double* grad_qd0, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* The backward pass of iLQR / DDP / time-varying LQR over a rollout: the Riccati recursion that turns the linearisation
+ * dc_du, Minv of rbd_rollout's steps and a quadratic cost model (diagonal state and control Hessians, a full terminal
+ * Hessian through P) into a feed-forward term k[t] [n] and feedback gains K[t] [n, 2n].  Fixed base only; a floating-base
+ * library returns RBD_ERR_UNSUPPORTED.  Conventions are rbd_rollout_adjoint's: time-major, slice t is x_{t+1} = (q | qd),
+ * state costs attach to slices and control costs to u[t].  With D = dc_du[t] and M = Minv[t] (symmetric):
+ *   A0 = [[I, dt I], [0, I]];  b = [dt^2 I ; dt I] (integrator 0) | [0 ; dt I] (integrator 1);  Bm = b M;  A = A0 - Bm D
+ * and, per row, carried lam [2n], P [2n, 2n], dV [2], status (int32), for t = T-1 ... 0:
+ *   lam += (gq[t] | gqd[t]);  P += diag(hq[t] | hqd[t])
+ *   Qx = A^T lam;  Qu = gu[t] + Bm^T lam;  Qxx = A^T P A;  Qux = Bm^T P A;  Quu = diag(hu[t]) + Bm^T P Bm
+ *   Cholesky of Quu + reg I;  k[t] = -(Quu + reg I)^-1 Qu;  K[t] = -(Quu + reg I)^-1 Qux
+ *   dV[0] += k^T Qu;  dV[1] += 1/2 k^T Quu k            (Quu without reg)
+ *   lam = Qx + K^T Quu k + K^T Qu + Qux^T k;  P = Qxx + K^T Quu K + K^T Qux + Qux^T K;  P = 1/2 (P + P^T)
+ * A pivot of the factorisation that is <= 0 or not finite: k[t] = 0 and K[t] = 0 are stored for that row and step,
+ * status += 1, lam = Qx, P = Qxx, dV unchanged; no other row is affected.  dV[0] + dV[1] is the expected change of cost of
+ * the closed-loop pass u = u + k + K dx.
+ * PRISMATIC JOINTS: rbd_rnea_grad's dc_dq reproduces the reference and is not the q-derivative for prismatic joints, and
+ * the gains of rbd_rollout_lqr inherit that: they belong to the true linearisation on robots with revolute joints only.
+ *
+ * rbd_rollout_riccati: the scan alone, ONE launch that walks the time axis with lam and P on chip and factors Quu on
+ * chip, for a caller that holds the linearisation.  Per row and step it reads 3 n^2 + 6n scalars and writes 2 n^2 + n.
+ *   dc_du [T, B, n, 2n], Minv [T, B, n, n] (dense, symmetric): step t's linearisation; T = the steps of THIS call
+ *   gq, gqd, hq, hqd : x_final_only == 0: [T, B, n]; != 0: [B, n], added at step T - 1 only (a caller that splits the
+ *                 time axis passes them to the call that holds the last step).  Any may be NULL = zero
+ *   gu          : [T, B, n] or NULL = zero
+ *   hu          : hu_shared == 0: [T, B, n]; != 0: [n], shared by every row and step.  Required
+ *   reg         : finite, >= 0
+ *   lam [B, 2n], P [B, 2n, 2n] (symmetric), dV [B, 2], status [B] (int32): IN and OUT, the value function after step T
+ *                 (zeros, or a terminal Hessian in P) -> after step 0.  They are loaded and stored as they are and every
+ *                 step runs the same instructions, so a scan split at any step -- the later steps first -- is
+ *                 bit-identical to the unsplit one
+ *   k [T, B, n], K [T, B, n, 2n]: OUT
+ * rbd_rollout_lqr: the composite.  q_traj, qd_traj [T, B, n] are rbd_rollout's trajectory (slice T - 1 is not read); it
+ * zeroes lam, P, dV and status (caller buffers) and walks chunks of Tc steps from the end exactly as rbd_rollout_grad
+ * does: rbd_aba, rbd_rnea_grad without damping and rbd_minv on the chunk's Tc B flat rows, then the scan; step 0 at
+ * (q0, qd0, u[0]) is its own last chunk.  Tc is the largest chunk (at most T - 1, at least 1) whose
+ * rbd_rollout_lqr_workspace_bytes(B, Tc, elem_size) fits ws_bytes.
+ * Arguments are checked before anything touches the GPU: null required pointer, B < 0, T < 0, dt or reg not finite,
+ * reg < 0, unknown integrator, B T n 2n too large, misaligned lam / P / dV / status / k / K / workspace: RBD_ERR_ARG; a
+ * workspace that does not hold one step: RBD_ERR_WORKSPACE; a robot whose step (8 n^2 scalars per row) does not fit 64 KiB
+ * of LDS in this precision: RBD_ERR_UNSUPPORTED.  B == 0 or T == 0 is a no-op: nothing is written. */
+int rbd_rollout_riccati_f32(const float* dc_du, const float* Minv, const float* gq, const float* gqd, const float* hq,
+                            const float* hqd, int x_final_only, const float* gu, const float* hu, int hu_shared, float reg,
+                            float dt, int integrator, int64_t B, int64_t T, float* lam, float* P, float* dV, int32_t* status,
+                            float* k, float* K, void* stream);
+int rbd_rollout_riccati_f64(const double* dc_du, const double* Minv, const double* gq, const double* gqd, const double* hq,
+                            const double* hqd, int x_final_only, const double* gu, const double* hu, int hu_shared, double reg,
+                            double dt, int integrator, int64_t B, int64_t T, double* lam, double* P, double* dV,
+                            int32_t* status, double* k, double* K, void* stream);
+size_t rbd_rollout_lqr_workspace_bytes(int64_t B, int64_t Tc, int elem_size);
+int rbd_rollout_lqr_f32(const float* q0, const float* qd0, const float* u, const float* q_traj, const float* qd_traj,
+                        const float* gq, const float* gqd, const float* hq, const float* hqd, int x_final_only,
+                        const float* gu, const float* hu, int hu_shared, float reg, float dt, float gravity, int integrator,
+                        int64_t B, int64_t T, float* k, float* K, float* lam, float* P, float* dV, int32_t* status, void* ws,
+                        size_t ws_bytes, void* stream);
+int rbd_rollout_lqr_f64(const double* q0, const double* qd0, const double* u, const double* q_traj, const double* qd_traj,
+                        const double* gq, const double* gqd, const double* hq, const double* hqd, int x_final_only,
+                        const double* gu, const double* hu, int hu_shared, double reg, double dt, double gravity,
+                        int integrator, int64_t B, int64_t T, double* k, double* K, double* lam, double* P, double* dV,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

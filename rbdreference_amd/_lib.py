@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "rbd_rollout_f32", "rbd_rollout_f64",
     "rbd_rollout_adjoint_f32", "rbd_rollout_adjoint_f64",
     "rbd_rollout_grad_workspace_bytes", "rbd_rollout_grad_f32", "rbd_rollout_grad_f64",
+    "rbd_rollout_riccati_f32", "rbd_rollout_riccati_f64",
+    "rbd_rollout_lqr_workspace_bytes", "rbd_rollout_lqr_f32", "rbd_rollout_lqr_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -141,6 +143,17 @@ def _declare(lib):
         f.restype = c_int
         f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ct, ct, c_int, c_int64, c_int64,
                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        costs = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ct]   # gq gqd hq hqd final gu hu shared reg
+        f = getattr(lib, f"rbd_rollout_riccati_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, *costs, ct, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                      c_void_p]
+        f = getattr(lib, f"rbd_rollout_lqr_{sfx}")
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, *costs, ct, ct, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.rbd_rollout_lqr_workspace_bytes.restype = c_size_t
+    lib.rbd_rollout_lqr_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_rollout_grad_workspace_bytes.restype = c_size_t
     lib.rbd_rollout_grad_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_fdsva_so_workspace_bytes.restype = c_size_t

@@ -1104,6 +1104,188 @@ class RBDReference:
                 RBD_INTEGRATORS[integrator], B, T, self._ptr(lam_t), self._ptr(gu), st))
         return (gu.cpu().numpy(), lam_t.cpu().numpy()) if is_np else (gu, lam_t)
 
+    # ---- backward pass of iLQR / DDP over a rollout: rbd_rollout_lqr (aba, rnea_grad, minv per chunk + the Riccati scan) ----
+    @staticmethod
+    def _lqr_cost_shapes(T, B, n, unb, who, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg):
+        """Shape and value checks of the cost model, before anything touches the GPU -> (x_final_only, hu_shared)."""
+        if hess_u is None:
+            raise ValueError(f"{who}: hess_u is required (the diagonal of the control cost's Hessian, [T, B, n] or [n])")
+        full, fin = ((T, n), (n,)) if unb else ((T, B, n), (B, n))
+        shapes = [tuple(np.shape(a)) for a in (grad_q, grad_qd, hess_q, hess_qd) if a is not None]
+        if any(sh not in (full, fin) for sh in shapes) or len(set(shapes)) > 1:
+            raise ValueError(f"{who}: grad_q, grad_qd, hess_q and hess_qd must all be {list(full)} or all {list(fin)} "
+                             f"(last step only), got {shapes}")
+        if grad_u is not None and tuple(np.shape(grad_u)) != full:
+            raise ValueError(f"{who}: grad_u must be {list(full)}, got {tuple(np.shape(grad_u))}")
+        sh = tuple(np.shape(hess_u))
+        if sh != (n,) and sh != full:          # (unbatched: [T, n] is per step, [n] is shared)
+            raise ValueError(f"{who}: hess_u must be {list(full)} or [{n}] (shared by every row and step), got {sh}")
+        if not (np.isfinite(reg) and reg >= 0):
+            raise ValueError(f"{who}: reg must be finite and >= 0, got {reg}")
+        return bool(shapes) and shapes[0] == fin, sh == (n,)
+
+    @staticmethod
+    def _lqr_dev_tensor(x, is_np, dev, dtp):
+        """An optional input of rollout_lqr / rollout_riccati as a contiguous device tensor of dtype ``dtp`` (int32 for
+        ``status``); numpy and torch inputs do not mix."""
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor):
+            if is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            if x.device != dev or x.dtype != dtp:
+                raise TypeError("all inputs must share device and dtype (status: int32)")
+            return x.contiguous()
+        if not is_np:
+            raise TypeError("mixing numpy and torch inputs is not supported")
+        return torch.as_tensor(np.asarray(x, dtype=np.int32 if dtp == torch.int32 else np.float64), device=dev).contiguous()
+
+    def rollout_lqr(self, q0, qd0, u, dt, grad_q=None, grad_qd=None, hess_q=None, hess_qd=None, grad_u=None, hess_u=None,
+                    reg=0.0, GRAVITY=-9.81, integrator="semi_implicit", q=None, qd=None, workspace_bytes=None):
+        """Backward pass of iLQR / DDP / time-varying LQR along a rollout: from the linearisation of every step and a
+        quadratic cost model -> ``(k [T, B, n], K [T, B, n, 2n], lam [B, 2n], P [B, 2n, 2n], dV [B, 2], status [B])``: the
+        feed-forward terms and feedback gains of ``u = u + alpha k + K dx``, the value function's gradient and Hessian
+        at the initial state, the expected cost change ``alpha dV[0] + alpha^2 dV[1]`` and, per row, the number of steps
+        whose ``Quu + reg I`` could not be factored (their ``k`` and ``K`` are zero).  Not part of the reference.
+
+        ``aba``, ``rnea_grad`` and ``minv`` run on the trajectory's flat rows per chunk of the horizon; the Riccati
+        recursion over time is then one HIP launch per chunk with ``lam`` and ``P`` on chip (``rbd_rollout_lqr.h``; the
+        recursion is written out in ``include/rbd_hip.h``).
+
+        Conventions are ``rollout_grad``'s: time-major, slice ``t`` is the state after step ``t + 1``; state costs attach
+        to slices, control costs to ``u[t]``.  ``grad_q, grad_qd, hess_q, hess_qd``: gradient and DIAGONAL Hessian of the
+        state cost, all ``[T, B, n]`` or all ``[B, n]`` (last slice only); any may be omitted.  ``grad_u [T, B, n]``
+        (optional), ``hess_u [T, B, n]`` or ``[n]`` (shared; required).  ``reg >= 0`` is added to ``Quu``'s diagonal in the
+        factorisation.  A shared ``u [T, n]`` is expanded; the gains stay per row.  ``q0 [n]`` with ``u [T, n]`` is one
+        row.  ``q, qd``: the trajectory ``rollout`` returned for these inputs; computed here when omitted.
+        ``workspace_bytes``: device scratch for the linearisation, which decides how many steps one chunk holds
+        (default: all of them, capped at 1 GiB).  A full terminal Hessian goes through ``rollout_riccati``'s ``P``.
+        numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
+
+        Robots with PRISMATIC joints: ``rnea_grad``'s ``dc_dq`` reproduces the reference and is not the q-derivative for
+        such joints (see ``rollout_grad``), and the gains inherit that: they belong to the true linearisation on robots
+        with revolute joints only.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        if self.model.floating:
+            raise NotImplementedError("rollout_lqr: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"rollout_lqr: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
+        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"rollout_lqr: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        unb = len(sq) == 1
+        B = 1 if unb else sq[0]
+        shared = len(su) == 2
+        if unb and not shared:
+            raise ValueError(f"rollout_lqr: q0 [{n}] takes u [T, {n}], got {su}")
+        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
+            raise ValueError(f"rollout_lqr: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
+        T = su[0]
+        if T == 0:
+            raise ValueError("rollout_lqr: u holds no step (T == 0)")
+        final, hu_shared = self._lqr_cost_shapes(T, B, n, unb, "rollout_lqr", grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg)
+        if (q is None) != (qd is None):
+            raise ValueError("rollout_lqr: give both q and qd (the trajectory of rollout) or neither")
+        traj = (T, n) if unb else (T, B, n)
+        if q is not None and (tuple(np.shape(q)) != traj or tuple(np.shape(qd)) != traj):
+            raise ValueError(f"rollout_lqr: q and qd must be the trajectory {list(traj)}, got {tuple(np.shape(q))} and {tuple(np.shape(qd))}")
+        if workspace_bytes is not None and int(workspace_bytes) < 0:
+            raise ValueError("rollout_lqr: workspace_bytes < 0")
+        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
+
+        dev_tensor = lambda x: self._lqr_dev_tensor(x, is_np, dev, dtp)      # noqa: E731
+        u, gq, gqd, hq, hqd, gu, hu, q, qd = (dev_tensor(x) for x in (u, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, q, qd))
+        esz = 4 if dtp == torch.float32 else 8
+        sfx = "f32" if esz == 4 else "f64"
+        with torch.cuda.device(dev):
+            if shared:
+                u = u[:, None, :].expand(T, B, n).contiguous()
+            if q is None:
+                q, qd = self.rollout(q0, qd0, u, dt, GRAVITY, integrator)
+            k = torch.empty((T, B, n), device=dev, dtype=dtp)
+            K = torch.empty((T, B, n, 2 * n), device=dev, dtype=dtp)
+            lam = torch.empty((B, 2 * n), device=dev, dtype=dtp)
+            P = torch.empty((B, 2 * n, 2 * n), device=dev, dtype=dtp)
+            dV = torch.empty((B, 2), device=dev, dtype=dtp)
+            status = torch.empty((B,), device=dev, dtype=torch.int32)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib = self._lib.resolve("rbd_rollout_lqr", sfx)     # ONE resolution: workspace size and entry point from the same library
+            if workspace_bytes is None:
+                wsb = int(lib.rbd_rollout_lqr_workspace_bytes(B, T, esz))
+                wsb = max(min(wsb, self._ROLLG_WS_CAP), int(lib.rbd_rollout_lqr_workspace_bytes(B, 1, esz)))
+            else:
+                wsb = int(workspace_bytes)
+            ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
+            self._lib.check(getattr(lib, f"rbd_rollout_lqr_{sfx}")(
+                self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(q), self._ptr(qd), self._ptr(gq), self._ptr(gqd),
+                self._ptr(hq), self._ptr(hqd), int(final), self._ptr(gu), self._ptr(hu), int(hu_shared), float(reg), float(dt),
+                float(GRAVITY), RBD_INTEGRATORS[integrator], B, T, self._ptr(k), self._ptr(K), self._ptr(lam), self._ptr(P),
+                self._ptr(dV), self._ptr(status), ws.data_ptr(), wsb, st))
+        out = (k, K, lam, P, dV, status)
+        if unb:
+            out = (k[:, 0], K[:, 0], lam[0], P[0], dV[0], status[0])
+        return tuple(x.cpu().numpy() for x in out) if is_np else out
+
+    def rollout_riccati(self, dc_du, Minv, dt, grad_q=None, grad_qd=None, hess_q=None, hess_qd=None, grad_u=None, hess_u=None,
+                        reg=0.0, integrator="semi_implicit", lam=None, P=None, dV=None, status=None):
+        """The scan of ``rollout_lqr`` alone (``rbd_rollout_riccati``), for a caller who holds the linearisation:
+        ``dc_du [T, B, n, 2n]`` (``rnea_grad``) and ``Minv [T, B, n, n]`` (dense, symmetric) of the ``T`` steps, time-major
+        -> ``(k [T, B, n], K [T, B, n, 2n], lam [B, 2n], P [B, 2n, 2n], dV [B, 2], status [B] int32)``.
+
+        ``lam, P, dV, status`` are the value function entering at the END of these steps (default zeros; a full terminal
+        Hessian, e.g. a Gauss-Newton ``J^T J``, goes in through ``P``, which must be symmetric) and are returned as they
+        leave at their beginning; contiguous tensors are updated in place.  A horizon may be split: the later steps first,
+        the four carried over, bit-identical to one call.  Costs as in ``rollout_lqr``; the ``[B, n]`` form of the state
+        costs belongs to the last of THESE steps.  numpy in -> float64 numpy out; tensors stay on their device and dtype
+        and run on torch's current stream.  The prismatic-joint caveat of ``rollout_grad`` applies to a linearisation
+        that comes from ``rnea_grad``.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        if self.model.floating:
+            raise NotImplementedError("rollout_riccati: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"rollout_riccati: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sd, sm = tuple(np.shape(dc_du)), tuple(np.shape(Minv))
+        if len(sd) != 4 or sd[2:] != (n, 2 * n) or sm != sd[:2] + (n, n):
+            raise ValueError(f"rollout_riccati: dc_du must be [T, B, {n}, {2 * n}] and Minv [T, B, {n}, {n}], got {sd} and {sm}")
+        T, B = sd[:2]
+        if T == 0:
+            raise ValueError("rollout_riccati: no step (T == 0)")
+        final, hu_shared = self._lqr_cost_shapes(T, B, n, False, "rollout_riccati", grad_q, grad_qd, hess_q, hess_qd, grad_u,
+                                                 hess_u, reg)
+        for name, x, sh in (("lam", lam, (B, 2 * n)), ("P", P, (B, 2 * n, 2 * n)), ("dV", dV, (B, 2)), ("status", status, (B,))):
+            if x is not None and tuple(np.shape(x)) != sh:
+                raise ValueError(f"rollout_riccati: {name} must be {list(sh)}, got {tuple(np.shape(x))}")
+        is_np = not isinstance(dc_du, torch.Tensor)
+        if is_np:
+            if not torch.cuda.is_available():
+                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
+            dev, dtp = torch.device("cuda", 0), torch.float64
+        else:
+            dev, dtp = dc_du.device, dc_du.dtype
+            if dev.type != "cuda":
+                raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
+            if dtp not in (torch.float32, torch.float64):
+                raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
+
+        dev_tensor = lambda x, dt_=dtp: self._lqr_dev_tensor(x, is_np, dev, dt_)      # noqa: E731
+        dc_du, Minv, gq, gqd, hq, hqd, gu, hu = (dev_tensor(x) for x in (dc_du, Minv, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u))
+        with torch.cuda.device(dev):
+            lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp) if lam is None else dev_tensor(lam)
+            P_t = torch.zeros((B, 2 * n, 2 * n), device=dev, dtype=dtp) if P is None else dev_tensor(P)
+            dV_t = torch.zeros((B, 2), device=dev, dtype=dtp) if dV is None else dev_tensor(dV)
+            st_t = torch.zeros((B,), device=dev, dtype=torch.int32) if status is None else dev_tensor(status, torch.int32)
+            k = torch.empty((T, B, n), device=dev, dtype=dtp)
+            K = torch.empty((T, B, n, 2 * n), device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_rollout_riccati", dtp)(
+                self._ptr(dc_du), self._ptr(Minv), self._ptr(gq), self._ptr(gqd), self._ptr(hq), self._ptr(hqd), int(final),
+                self._ptr(gu), self._ptr(hu), int(hu_shared), float(reg), float(dt), RBD_INTEGRATORS[integrator], B, T,
+                self._ptr(lam_t), self._ptr(P_t), self._ptr(dV_t), self._ptr(st_t), self._ptr(k), self._ptr(K), st))
+        out = (k, K, lam_t, P_t, dV_t, st_t)
+        return tuple(x.cpu().numpy() for x in out) if is_np else out
+
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):
         """Site table of a selection, resolved once and cached: ``(chunks of (site_body int32 [k], site_T float64 [k, 12]),

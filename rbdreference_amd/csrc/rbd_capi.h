@@ -705,7 +705,7 @@ struct RollgWorkspace {
 };
 #endif
 
-#ifdef RBD_NEED_ROLLG
+#if defined(RBD_NEED_ROLLG) || defined(RBD_NEED_LQR)
 // (rbd_aba of the FD unit, as the overloads of RBD_CROSS_UNIT)
 inline int rbd_aba(const float* q, const float* qd, const float* tau, float g, int64_t B, float* qdd, void* s) {
   return rbd_aba_f32(q, qd, tau, g, B, qdd, s);
@@ -713,6 +713,8 @@ inline int rbd_aba(const float* q, const float* qd, const float* tau, float g, i
 inline int rbd_aba(const double* q, const double* qd, const double* tau, double g, int64_t B, double* qdd, void* s) {
   return rbd_aba_f64(q, qd, tau, g, B, qdd, s);
 }
+#endif
+#ifdef RBD_NEED_ROLLG
 // what rbd_rollout_adjoint and rbd_rollout_grad refuse alike, before any launch
 template <class T>
 int rollg_check(const char* who, T dt, int integrator, int64_t B, int64_t steps) {
@@ -806,6 +808,133 @@ int rollout_grad_launch(const T* q0, const T* qd0, const T* u, const T* q_traj, 
   return chunk(q0, qd0, 0, 1);
 }
 #endif  // RBD_NEED_ROLLG
+
+// rbd_rollout_lqr's workspace for chunks of Tc steps, R = Tc B flat rows: minv's scratch | qdd [R, N] | dc_du [R, N, 2N] |
+// Minv [R, N, N] (lam, P, dV and status are the caller's)
+#if defined(RBD_TU_COMMON) || defined(RBD_NEED_LQR)
+constexpr int64_t LQR_MAX_ROWS = (int64_t)1 << 30;        // rows of one chunk, and B: every launcher's grid holds them
+template <class T>
+struct LqrWorkspace {
+  size_t minv_ws_bytes, off_qdd, off_dcdu, off_minv, total;
+  LqrWorkspace(int64_t B, int64_t Tc) {
+    using namespace rbdk;
+    const size_t R = (size_t)B * (size_t)Tc;
+    size_t o = 0;
+    minv_ws_bytes = R * MINV_WS_PER_CFG * sizeof(T);
+    o += align16(minv_ws_bytes);
+    off_qdd = o;  o += align16(R * N * sizeof(T));
+    off_dcdu = o; o += align16(R * 2 * N * N * sizeof(T));
+    off_minv = o; o += align16(R * N * N * sizeof(T));
+    total = o;
+  }
+};
+#endif
+
+#ifdef RBD_NEED_LQR
+// what rbd_rollout_riccati and rbd_rollout_lqr refuse alike, before any launch
+template <class T>
+int lqr_check(const char* who, T reg, T dt, int integrator, int64_t B, int64_t steps) {
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "%s: fixed-base robots only", who);
+  if (B < 0) return fail(RBD_ERR_ARG, "%s: B < 0", who);
+  if (steps < 0) return fail(RBD_ERR_ARG, "%s: T < 0", who);
+  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "%s: dt must be finite", who);
+  if (!(reg - reg == T(0)) || reg < T(0)) return fail(RBD_ERR_ARG, "%s: reg must be finite and >= 0", who);
+  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
+    return fail(RBD_ERR_ARG, "%s: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)", who);
+  return 0;
+}
+// B T n 2n elements of dc_du and of K, B 2n 2n of P: byte offsets stay far inside int64; then what the kernel itself needs
+template <class T>
+int lqr_check_size(const char* who, int64_t B, int64_t steps) {
+  if (B > LQR_MAX_ROWS) return fail(RBD_ERR_ARG, "%s: B too large", who);
+  if (steps > (INT64_MAX / 64) / (B * rbdk::N * 2 * rbdk::N)) return fail(RBD_ERR_ARG, "%s: B * T * n * 2n too large", who);
+  if (!rbdk::lqr_fits<T>())
+    return fail(RBD_ERR_UNSUPPORTED, "%s: the step's matrices (8 n^2 scalars per row) do not fit LDS for this robot size and precision", who);
+  return 0;
+}
+
+// the scan (rbd_rollout_lqr.h): one launch for `steps` steps
+template <class T>
+int lqr_scan(const char* who, const T* dc_du, const T* Minv, const T* gq, const T* gqd, const T* hq, const T* hqd, int x_final_only,
+             const T* gu, const T* hu, int hu_shared, T reg, T dt, int integrator, int64_t B, int64_t steps, T* lam, T* P, T* dV,
+             int32_t* status, T* k, T* K, void* stream) {
+  using namespace rbdk;
+  unsigned grid;
+  if (int rc = grid_for(B, lqr_cfgs(), who, &grid)) return rc;
+  return launch(who, rollout_riccati_kernel<T>, grid, lqr_threads(), 0, stream, dc_du, Minv, gq, gqd, hq, hqd, x_final_only ? 1 : 0,
+                gu, hu, hu_shared ? 1 : 0, reg, dt, integrator, B, steps, lam, P, dV, reinterpret_cast<int*>(status), k, K);
+}
+
+template <class T>
+int rollout_riccati_launch(const T* dc_du, const T* Minv, const T* gq, const T* gqd, const T* hq, const T* hqd, int x_final_only,
+                           const T* gu, const T* hu, int hu_shared, T reg, T dt, int integrator, int64_t B, int64_t steps, T* lam,
+                           T* P, T* dV, int32_t* status, T* k, T* K, void* stream) {
+  if (int rc = lqr_check<T>("rbd_rollout_riccati", reg, dt, integrator, B, steps)) return rc;
+  if (B == 0 || steps == 0) return 0;
+  if (!dc_du || !Minv || !hu || !lam || !P || !dV || !status || !k || !K)
+    return fail(RBD_ERR_ARG, "rbd_rollout_riccati: dc_du, Minv, hu, lam, P, dV, status, k and K must be non-null");
+  if (misaligned(lam, P, dV, status, k, K)) return fail(RBD_ERR_ARG, "rbd_rollout_riccati: output buffers must be 16-byte aligned");
+  if (int rc = lqr_check_size<T>("rbd_rollout_riccati", B, steps)) return rc;
+  return lqr_scan<T>("rbd_rollout_riccati launch", dc_du, Minv, gq, gqd, hq, hqd, x_final_only, gu, hu, hu_shared, reg, dt,
+                     integrator, B, steps, lam, P, dV, status, k, K, stream);
+}
+
+// rbd_rollout_lqr: lam = P = dV = status = 0, then chunks of the time axis from the end as rbd_rollout_grad walks them -- aba,
+// rnea_grad, minv on the chunk's flat rows (the existing entry points, on the caller's stream), then the scan.  Step 0 is
+// linearised at (q0, qd0, u[0]): its own chunk.
+template <class T>
+int rollout_lqr_launch(const T* q0, const T* qd0, const T* u, const T* q_traj, const T* qd_traj, const T* gq, const T* gqd,
+                       const T* hq, const T* hqd, int x_final_only, const T* gu, const T* hu, int hu_shared, T reg, T dt, T gravity,
+                       int integrator, int64_t B, int64_t steps, T* k, T* K, T* lam, T* P, T* dV, int32_t* status, void* workspace,
+                       size_t wsb, void* stream) {
+  using namespace rbdk;
+  if (int rc = lqr_check<T>("rbd_rollout_lqr", reg, dt, integrator, B, steps)) return rc;
+  if (B == 0 || steps == 0) return 0;
+  if (!q0 || !qd0 || !u || !q_traj || !qd_traj || !hu || !k || !K || !lam || !P || !dV || !status)
+    return fail(RBD_ERR_ARG, "rbd_rollout_lqr: q0, qd0, u, q_traj, qd_traj, hu, k, K, lam, P, dV and status must be non-null");
+  if (misaligned(k, K, lam, P, dV, status)) return fail(RBD_ERR_ARG, "rbd_rollout_lqr: output buffers must be 16-byte aligned");
+  if (int rc = lqr_check_size<T>("rbd_rollout_lqr", B, steps)) return rc;
+  if (!workspace || wsb < LqrWorkspace<T>(B, 1).total)
+    return fail(RBD_ERR_WORKSPACE, "rbd_rollout_lqr: workspace missing or smaller than rbd_rollout_lqr_workspace_bytes(B, 1, .)");
+  if (misaligned(workspace)) return fail(RBD_ERR_ARG, "rbd_rollout_lqr: workspace must be 16-byte aligned");
+  // the largest chunk that fits (the size grows with Tc)
+  int64_t Tc = 1, hi_tc = steps - 1 < LQR_MAX_ROWS / B ? steps - 1 : LQR_MAX_ROWS / B;
+  while (Tc < hi_tc) {
+    const int64_t mid = Tc + (hi_tc - Tc + 1) / 2;
+    if (LqrWorkspace<T>(B, mid).total <= wsb) Tc = mid; else hi_tc = mid - 1;
+  }
+  const LqrWorkspace<T> L(B, Tc);
+  char* w = reinterpret_cast<char*>(workspace);
+  T* qdd = reinterpret_cast<T*>(w + L.off_qdd);
+  T* dc = reinterpret_cast<T*>(w + L.off_dcdu);
+  T* Mi = reinterpret_cast<T*>(w + L.off_minv);
+  hipError_t e = hipMemsetAsync(lam, 0, (size_t)B * 2 * N * sizeof(T), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(P, 0, (size_t)B * 4 * N * N * sizeof(T), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(dV, 0, (size_t)B * 2 * sizeof(T), (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "rbd_rollout_lqr (zeroing the value function)");
+  const int64_t row = B * N;
+  // steps [lo, hi) at rows q, qd; the state costs are dense [T, B, N] or belong to step T - 1 alone
+  auto chunk = [&](const T* q, const T* qd, int64_t lo, int64_t hi) {
+    const int64_t R = (hi - lo) * B;
+    const bool last = hi == steps;
+    auto at = [&](const T* a) { return x_final_only ? (last ? a : nullptr) : (a ? a + lo * row : nullptr); };
+    int rc;
+    if ((rc = rbd_aba(q, qd, u + lo * row, gravity, R, qdd, stream)) != 0) return rc;
+    if ((rc = rbd_rnea_grad(q, qd, qdd, gravity, 0, R, nullptr, dc, stream)) != 0) return rc;
+    if ((rc = rbd_minv(q, R, 1, Mi, w, L.minv_ws_bytes, stream)) != 0) return rc;
+    return lqr_scan<T>("rbd_rollout_lqr (scan) launch", dc, Mi, at(gq), at(gqd), at(hq), at(hqd), x_final_only,
+                       gu ? gu + lo * row : nullptr, hu_shared ? hu : hu + lo * row, hu_shared, reg, dt, integrator, B, hi - lo, lam,
+                       P, dV, status, k + lo * row, K + lo * row * 2 * N, stream);
+  };
+  for (int64_t hi = steps; hi > 1;) {
+    const int64_t lo = hi - Tc > 1 ? hi - Tc : 1;
+    if (int rc = chunk(q_traj + (lo - 1) * row, qd_traj + (lo - 1) * row, lo, hi)) return rc;
+    hi = lo;
+  }
+  return chunk(q0, qd0, 0, 1);
+}
+#endif  // RBD_NEED_LQR
 
 #ifdef RBD_NEED_EE
 // rbd_ee_pose: site table (host arrays) -> EeSites kernel argument; one launch for pose, gradient or both
@@ -1069,6 +1198,27 @@ RBD_DECLS_SELECTION(f64)
   int rbd_rollout_grad_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, T, T, int, int64_t,      \
                              int64_t, T*, T*, T*, void*, size_t, void*) RBD_STUB_BODY("rbd_rollout_grad")
 
+#define RBD_DEFS_LQR(SFX, T)                                                                                                     \
+  int rbd_rollout_riccati_##SFX(const T* dc_du, const T* Minv, const T* gq, const T* gqd, const T* hq, const T* hqd,             \
+                                int x_final_only, const T* gu, const T* hu, int hu_shared, T reg, T dt, int integrator,          \
+                                int64_t B, int64_t steps, T* lam, T* P, T* dV, int32_t* status, T* k, T* K, void* stream) {      \
+    RBD_ENTER rollout_riccati_launch<T>(dc_du, Minv, gq, gqd, hq, hqd, x_final_only, gu, hu, hu_shared, reg, dt, integrator, B,  \
+                                        steps, lam, P, dV, status, k, K, stream);                                                \
+  }                                                                                                                              \
+  int rbd_rollout_lqr_##SFX(const T* q0, const T* qd0, const T* u, const T* q_traj, const T* qd_traj, const T* gq, const T* gqd, \
+                            const T* hq, const T* hqd, int x_final_only, const T* gu, const T* hu, int hu_shared, T reg, T dt,   \
+                            T gravity, int integrator, int64_t B, int64_t steps, T* k, T* K, T* lam, T* P, T* dV,                \
+                            int32_t* status, void* ws, size_t ws_bytes, void* stream) {                                          \
+    RBD_ENTER rollout_lqr_launch<T>(q0, qd0, u, q_traj, qd_traj, gq, gqd, hq, hqd, x_final_only, gu, hu, hu_shared, reg, dt,     \
+                                    gravity, integrator, B, steps, k, K, lam, P, dV, status, ws, ws_bytes, stream);              \
+  }
+#define RBD_STUBS_LQR(SFX, T)                                                                                                    \
+  int rbd_rollout_riccati_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, int, const T*, const T*, int, T, T,  \
+                                int, int64_t, int64_t, T*, T*, T*, int32_t*, T*, T*, void*) RBD_STUB_BODY("rbd_rollout_riccati") \
+  int rbd_rollout_lqr_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, int,       \
+                            const T*, const T*, int, T, T, T, int, int64_t, int64_t, T*, T*, T*, T*, T*, int32_t*, void*, size_t, \
+                            void*) RBD_STUB_BODY("rbd_rollout_lqr")
+
 #if defined(RBD_TU_RNEA_F32)
 RBD_DEFS_RNEA(f32, float)
 #elif defined(RBD_STUB_RNEA_F32)
@@ -1181,6 +1331,17 @@ RBD_DEFS_ROLLG(f64, double)
 RBD_STUBS_ROLLG(f64, double)
 #endif
 
+#if defined(RBD_TU_LQR_F32)
+RBD_DEFS_LQR(f32, float)
+#elif defined(RBD_STUB_LQR_F32)
+RBD_STUBS_LQR(f32, float)
+#endif
+#if defined(RBD_TU_LQR_F64)
+RBD_DEFS_LQR(f64, double)
+#elif defined(RBD_STUB_LQR_F64)
+RBD_STUBS_LQR(f64, double)
+#endif
+
 #ifdef RBD_TU_COMMON
 int rbd_abi_version(void) { return RBD_ABI_VERSION; }
 const char* rbd_last_error(void) { return rbd_err_buf(); }
@@ -1257,6 +1418,12 @@ size_t rbd_rollout_grad_workspace_bytes(int64_t B, int64_t Tc, int elem_size) {
   if (B <= 0 || Tc <= 0 || rbdm::FLOATING_BASE || B > ROLLG_MAX_ROWS || Tc > ROLLG_MAX_ROWS / B) return 0;
   if (elem_size == 4) return RollgWorkspace<float>(B, Tc).total;
   if (elem_size == 8) return RollgWorkspace<double>(B, Tc).total;
+  return 0;
+}
+size_t rbd_rollout_lqr_workspace_bytes(int64_t B, int64_t Tc, int elem_size) {
+  if (B <= 0 || Tc <= 0 || rbdm::FLOATING_BASE || B > LQR_MAX_ROWS || Tc > LQR_MAX_ROWS / B) return 0;
+  if (elem_size == 4) return LqrWorkspace<float>(B, Tc).total;
+  if (elem_size == 8) return LqrWorkspace<double>(B, Tc).total;
   return 0;
 }
 #endif  // RBD_TU_COMMON

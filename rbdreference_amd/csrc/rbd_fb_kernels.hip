@@ -371,6 +371,15 @@ RBD_DECLS_SELECTION(f64)
                              int64_t, T*, T*, T*, void*, size_t, void*) {                                                   \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_grad: fixed-base robots only (rbd_rollout has no floating base)");       \
   }                                                                                                                         \
+  int rbd_rollout_riccati_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, int, const T*, const T*, int, T, T, \
+                                int, int64_t, int64_t, T*, T*, T*, int32_t*, T*, T*, void*) {                               \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_riccati: fixed-base robots only (rbd_rollout has no floating base)");    \
+  }                                                                                                                         \
+  int rbd_rollout_lqr_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, int,  \
+                            const T*, const T*, int, T, T, T, int, int64_t, int64_t, T*, T*, T*, T*, T*, int32_t*, void*,   \
+                            size_t, void*) {                                                                                \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_lqr: fixed-base robots only (rbd_rollout has no floating base)");        \
+  }                                                                                                                         \
   int rbd_aba_##SFX(const T*, const T*, const T*, T, int64_t, T*, void*) { return unsupported("rbd_aba"); }                 \
   int rbd_forward_dynamics_grad_##SFX(const T* q, const T* qd, const T* u, T gravity, int64_t B, T* qdd, T* dqdd_du, void* ws, \
                                       size_t wsb, void* stream) {                                                           \
