@@ -446,6 +446,45 @@ int rbd_rollout_lqr_f64(const double* q0, const double* qd0, const double* u, co
                         int integrator, int64_t B, int64_t T, double* k, double* K, double* lam, double* P, double* dV,
                         int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* Closed-loop rollout: the forward pass that consumes the k, K of rbd_rollout_lqr -- an iLQR / DDP line search, a
+ * time-varying LQR tracking controller, roll-outs from perturbed initial states around one feedback policy -- T steps in ONE
+ * launch with the control law inside the time loop.  Fixed base only; a floating-base library returns RBD_ERR_UNSUPPORTED.
+ * Integrators and conventions are rbd_rollout's.  Write x = (q | qd).  The state at which u[t] acts is x_t: x_0 = (q0, qd0),
+ * x_t = slice t - 1 of the trajectory for t >= 1; the reference state xref_t follows the same rule with (q0_ref, qd0_ref) and
+ * (q_ref, qd_ref).  Per row and step:
+ *   dx  = x_t - xref_t
+ *   u_t = u[t] + alpha k[t] + K[t] dx          (K[t] is n x 2n; one chain of fused multiply-adds per joint, in that order)
+ *   u_t = u_t < u_lo ? u_lo : (u_t > u_hi ? u_hi : u_t)      per joint, when limits are given; a NaN stays a NaN
+ *   qdd = aba(q_t, qd_t, u_t, gravity), then the integrator's two fused multiply-adds
+ * SHARED NOMINAL: the rollout has B rows, the nominal B_nom rows, B a multiple of B_nom; row r reads row r % B_nom of u, k, K,
+ * q0_ref, qd0_ref, q_ref, qd_ref and its own q0[r], qd0[r], alpha[r].  B_nom == B is the plain case; a line search over A
+ * step sizes is B = A B_nom; many starts around one policy is B_nom = 1.  A row's arithmetic does not depend on B_nom: a
+ * shared launch is bit-identical to the unshared one on the tiled nominal.
+ *   q0, qd0            : [B, n] device, the state before step 0; never written
+ *   u, k, K            : [T, B_nom, n], [T, B_nom, n] or NULL (no feed-forward term), [T, B_nom, n, 2n]
+ *   q0_ref, qd0_ref    : [B_nom, n]
+ *   q_ref, qd_ref      : [T, B_nom, n], what rbd_rollout returned for the nominal; slice T - 1 is never read
+ *   alpha              : [B] device; NULL exactly when k is NULL
+ *   u_lo, u_hi         : [n] device, or both NULL (no limits)
+ *   q_out, qd_out      : trajectory != 0: [T, B, n], slice t = the state after step t + 1; trajectory == 0: [B, n], the final
+ *                        state only
+ *   u_out              : [T, B, n], the controls actually applied, or NULL
+ * Per row and step it reads 2 n^2 + 4n scalars (the 2 n^2 of K shared by the rows of one nominal row) and writes up to 3n.
+ * Arguments are checked before anything touches the GPU: null required pointer, k xor alpha null, u_lo xor u_hi null, B < 0,
+ * T < 0, B > 0 with B_nom <= 0 or B not a multiple of B_nom, dt not finite, unknown integrator, misaligned output, B or
+ * B T n or B_nom T n 2n too large: RBD_ERR_ARG; a robot whose state (17 scalars per body and row) exceeds the LDS:
+ * RBD_ERR_UNSUPPORTED.  B == 0 or T == 0 is a no-op: nothing is written. */
+int rbd_rollout_closed_loop_f32(const float* q0, const float* qd0, const float* u, const float* k, const float* K,
+                                const float* q0_ref, const float* qd0_ref, const float* q_ref, const float* qd_ref,
+                                const float* alpha, const float* u_lo, const float* u_hi, float dt, float gravity,
+                                int integrator, int64_t B, int64_t B_nom, int64_t T, float* q_out, float* qd_out,
+                                int trajectory, float* u_out, void* stream);
+int rbd_rollout_closed_loop_f64(const double* q0, const double* qd0, const double* u, const double* k, const double* K,
+                                const double* q0_ref, const double* qd0_ref, const double* q_ref, const double* qd_ref,
+                                const double* alpha, const double* u_lo, const double* u_hi, double dt, double gravity,
+                                int integrator, int64_t B, int64_t B_nom, int64_t T, double* q_out, double* qd_out,
+                                int trajectory, double* u_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

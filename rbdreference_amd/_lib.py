@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "rbd_rollout_grad_workspace_bytes", "rbd_rollout_grad_f32", "rbd_rollout_grad_f64",
     "rbd_rollout_riccati_f32", "rbd_rollout_riccati_f64",
     "rbd_rollout_lqr_workspace_bytes", "rbd_rollout_lqr_f32", "rbd_rollout_lqr_f64",
+    "rbd_rollout_closed_loop_f32", "rbd_rollout_closed_loop_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -152,6 +153,9 @@ def _declare(lib):
         f.restype = c_int
         f.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, *costs, ct, ct, c_int, c_int64, c_int64, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        f = getattr(lib, f"rbd_rollout_closed_loop_{sfx}")
+        f.restype = c_int
+        f.argtypes = [*[c_void_p] * 12, ct, ct, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.rbd_rollout_lqr_workspace_bytes.restype = c_size_t
     lib.rbd_rollout_lqr_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_rollout_grad_workspace_bytes.restype = c_size_t

@@ -936,6 +936,116 @@ class RBDReference:
             q, qd = q.squeeze(-2), qd.squeeze(-2)
         return (q.cpu().numpy(), qd.cpu().numpy()) if is_np else (q, qd)
 
+    # ---- closed-loop rollouts: rbd_rollout_closed_loop, the control law u = u + alpha k + K dx inside the time loop ----
+    def rollout_closed_loop(self, q0, qd0, u, q_ref, qd_ref, K, dt, k=None, alpha=1.0, q0_ref=None, qd0_ref=None,
+                            u_min=None, u_max=None, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True):
+        """The forward pass that consumes ``rollout_lqr``'s gains, in ONE kernel launch -> ``(q, qd, u_applied)``: an
+        iLQR / DDP line search, a time-varying LQR tracking controller, roll-outs around a feedback policy.  Not part of
+        the reference.  With ``x = (q | qd)``, per row and step
+
+            ``dx = x_t - xref_t``;  ``u_t = u[t] + alpha k[t] + K[t] dx``;  clipped to ``[u_min, u_max]`` per joint when
+            limits are given (a NaN stays a NaN);  ``qdd = aba(q_t, qd_t, u_t, GRAVITY)``, then ``rollout``'s integrator
+
+        where ``x_0 = (q0, qd0)`` and ``x_t`` is slice ``t - 1`` of the trajectory, and the reference state ``xref_t``
+        follows the same rule: ``(q0_ref, qd0_ref)`` -- by default ``(q0, qd0)``, so ``dx_0 = 0``, the iLQR case -- then
+        slice ``t - 1`` of ``(q_ref, qd_ref)``, which are exactly what ``rollout`` returned for the nominal (their last
+        slice is never read).
+
+        Time-major like ``rollout``: ``q0, qd0 [B, n]``, ``u, q_ref, qd_ref [T, B, n]``, ``K [T, B, n, 2n]`` (the layout
+        ``rollout_lqr`` returns), ``k [T, B, n]`` or ``None`` (no feed-forward term), ``u_min, u_max``: scalars or ``[n]``,
+        both or neither.  A float ``alpha`` gives ``q, qd, u_applied [T, B, n]`` (``q, qd [B, n]`` with
+        ``trajectory=False``; ``u_applied``, the controls actually applied, is ``[T, B, n]`` either way).  A 1-D ``alpha``
+        of length ``A`` (sequence, array or tensor) is a line search: ``A B`` rows run against the one nominal -- every
+        candidate shares its ``K`` stream -- and the outputs are ``[T, A, B, n]`` (final state ``[A, B, n]``).  Unbatched
+        inputs (``q0 [n]``, ``u [T, n]``, ``K [T, n, 2n]``) drop the ``B`` axis.  numpy in -> float64 numpy out; tensors
+        stay on their device and dtype and run on torch's current stream.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        who = "rollout_closed_loop"
+        if self.model.floating:
+            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        n = self.n
+        sq = tuple(np.shape(q0))                  # shapes first: refused before anything touches the GPU
+        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"{who}: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        unb = len(sq) == 1
+        lead = () if unb else (sq[0],)
+        B = 1 if unb else sq[0]
+        su = tuple(np.shape(u))
+        if len(su) != len(lead) + 2 or su[1:] != lead + (n,):
+            raise ValueError(f"{who}: u must be {['T', *lead, n]} (time-major), got {su}")
+        T = su[0]
+        if T == 0:
+            raise ValueError(f"{who}: u holds no step (T == 0)")
+        for name, x, want in (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
+                              ("q0_ref", q0_ref, sq), ("qd0_ref", qd0_ref, sq)):
+            if x is None:
+                if name in ("q_ref", "qd_ref", "K"):
+                    raise ValueError(f"{who}: {name} is required")
+                continue
+            if tuple(np.shape(x)) != want:
+                raise ValueError(f"{who}: {name} must be {list(want)}, got {tuple(np.shape(x))}")
+        if (q0_ref is None) != (qd0_ref is None):
+            raise ValueError(f"{who}: give q0_ref and qd0_ref together, or neither (they default to q0, qd0)")
+        if (u_min is None) != (u_max is None):
+            raise ValueError(f"{who}: give u_min and u_max together, or neither")
+        for name, x in (("u_min", u_min), ("u_max", u_max)):
+            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
+                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
+        sa = tuple(np.shape(alpha))
+        if len(sa) > 1 or (len(sa) == 1 and sa[0] == 0):
+            raise ValueError(f"{who}: alpha must be a float or a non-empty 1-D sequence of step sizes, got shape {sa}")
+        A = sa[0] if sa else None
+        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
+
+        def dev_of(x, dtype=None):
+            if isinstance(x, torch.Tensor):
+                if is_np:
+                    raise TypeError("mixing numpy and torch inputs is not supported")
+                if x.device != dev or x.dtype != dtp:
+                    raise TypeError("all inputs must share device and dtype")
+                return x.contiguous()
+            if not is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
+
+        u, q_ref, qd_ref, K = (dev_of(x) for x in (u, q_ref, qd_ref, K))
+        k = None if k is None else dev_of(k)
+        q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (dev_of(q0_ref), dev_of(qd0_ref))
+        with torch.cuda.device(dev):
+            lims = [None, None]
+            if u_min is not None:
+                for i, x in enumerate((u_min, u_max)):
+                    x = x.to(device=dev, dtype=dtp) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
+                    lims[i] = x.expand(n).contiguous()
+            rows = B * (A or 1)
+            if A is not None:
+                q0, qd0 = q0.repeat(A, 1), qd0.repeat(A, 1)          # row a B + b starts where row b does
+            al = None
+            if k is not None:
+                if A is None:
+                    al = torch.full((rows,), float(alpha), device=dev, dtype=dtp)
+                else:
+                    a1 = alpha.to(device=dev, dtype=dtp) if isinstance(alpha, torch.Tensor) else torch.as_tensor(np.asarray(alpha, dtype=np.float64), device=dev).to(dtp)
+                    al = a1.repeat_interleave(B).contiguous()
+            q = torch.empty((T, rows, n) if trajectory else (rows, n), device=dev, dtype=dtp)
+            qd = torch.empty_like(q)
+            ua = torch.empty((T, rows, n), device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_rollout_closed_loop", dtp)(
+                self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(k), self._ptr(K), self._ptr(q0_ref), self._ptr(qd0_ref),
+                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(lims[0]), self._ptr(lims[1]), float(dt), float(GRAVITY),
+                RBD_INTEGRATORS[integrator], rows, B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), self._ptr(ua), st))
+        outs = []
+        for x in (q, qd, ua):
+            if A is not None:
+                x = x.view(*x.shape[:-2], A, B, n)
+            if unb:
+                x = x.squeeze(-2)
+            outs.append(x.cpu().numpy() if is_np else x)
+        return tuple(outs)
+
     # ---- reverse-mode gradient of a rollout: rbd_rollout_grad (aba, rnea_grad, minv per chunk + one scan launch) ------
     _ROLLG_WS_CAP = 1 << 30
 

@@ -683,6 +683,44 @@ int rollout_launch(const T* q0, const T* qd0, const T* u, int u_shared, T dt, T 
 }
 #endif  // RBD_NEED_ROLL
 
+#ifdef RBD_NEED_ROLLCL
+// rbd_rollout_closed_loop: one launch for all T steps, the control law inside the time loop (rbd_rollout_cl.h).  Arguments
+// are checked before the launch.
+template <class T>
+int rollout_cl_launch(const T* q0, const T* qd0, const T* u, const T* k, const T* K, const T* q0_ref, const T* qd0_ref,
+                      const T* q_ref, const T* qd_ref, const T* alpha, const T* u_lo, const T* u_hi, T dt, T gravity,
+                      int integrator, int64_t B, int64_t B_nom, int64_t steps, T* q_out, T* qd_out, int trajectory, T* u_out,
+                      void* stream) {
+  using namespace rbdk;
+  const char* who = "rbd_rollout_closed_loop";
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "%s: fixed-base robots only", who);
+  if (B < 0) return fail(RBD_ERR_ARG, "%s: B < 0", who);
+  if (steps < 0) return fail(RBD_ERR_ARG, "%s: T < 0", who);
+  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "%s: dt must be finite", who);
+  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
+    return fail(RBD_ERR_ARG, "%s: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)", who);
+  if (B == 0 || steps == 0) return 0;
+  if (B_nom <= 0 || B % B_nom != 0) return fail(RBD_ERR_ARG, "%s: B_nom must be positive and divide B", who);
+  if (!q0 || !qd0 || !u || !K || !q0_ref || !qd0_ref || !q_ref || !qd_ref || !q_out || !qd_out)
+    return fail(RBD_ERR_ARG, "%s: q0, qd0, u, K, q0_ref, qd0_ref, q_ref, qd_ref, q_out and qd_out must be non-null", who);
+  if ((k == nullptr) != (alpha == nullptr)) return fail(RBD_ERR_ARG, "%s: k and alpha must be both null or both non-null", who);
+  if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(RBD_ERR_ARG, "%s: u_lo and u_hi must be both null or both non-null", who);
+  if (misaligned(q_out, qd_out, u_out)) return fail(RBD_ERR_ARG, "%s: output buffers must be 16-byte aligned", who);
+  unsigned grid;
+  if (int rc = grid_for(B, ABA_PARK ? rollcl_lanes<T>() : 64, who, &grid)) return rc;
+  // B T n elements of each trajectory, B_nom T n 2n of K: byte offsets stay far inside int64
+  if (steps > (INT64_MAX / 64) / (B * N)) return fail(RBD_ERR_ARG, "%s: B * T * n too large", who);
+  if (steps > (INT64_MAX / 64) / (B_nom * N * 2 * N)) return fail(RBD_ERR_ARG, "%s: B_nom * T * n * 2n too large", who);
+  constexpr size_t lds = rollcl_lds_bytes<T>();
+  if (lds > LDS_MAX) return fail(RBD_ERR_UNSUPPORTED, "%s: per-body state does not fit LDS for this robot size", who);
+  const long long row = (long long)B * N;
+  const int aligned = (row * (long long)sizeof(T)) % 16 == 0;      // every trajectory slice starts on a 16-byte boundary
+  return launch("rbd_rollout_closed_loop launch", rollout_closed_loop_kernel<T>, grid, ROLLCL_THREADS, lds, stream, q0, qd0, u, k, K, q0_ref,
+                qd0_ref, q_ref, qd_ref, alpha, u_lo, u_hi, dt, gravity, integrator, B, B_nom, steps, q_out, qd_out,
+                trajectory ? 1 : 0, u_out, row, aligned);
+}
+#endif  // RBD_NEED_ROLLCL
+
 // rbd_rollout_grad's workspace for chunks of Tc steps, R = Tc B flat rows: minv's scratch | qdd [R, N] | dc_du [R, N, 2N] |
 // Minv [R, N, N] | lam [B, 2N]
 #if defined(RBD_TU_COMMON) || defined(RBD_NEED_ROLLG)
@@ -1181,7 +1219,20 @@ RBD_DECLS_SELECTION(f64)
 #define RBD_STUBS_ROLL(SFX, T)                                                                                                   \
   int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) RBD_STUB_BODY("rbd_rollout")
 
-#define RBD_DEFS_ROLLG(SFX, T)                                                                                                   \
+#define RBD_DEFS_ROLLCL(SFX, T)                                                                                                  \
+  int rbd_rollout_closed_loop_##SFX(const T* q0, const T* qd0, const T* u, const T* k, const T* K, const T* q0_ref,              \
+                                    const T* qd0_ref, const T* q_ref, const T* qd_ref, const T* alpha, const T* u_lo,            \
+                                    const T* u_hi, T dt, T gravity, int integrator, int64_t B, int64_t B_nom, int64_t steps,     \
+                                    T* q_out, T* qd_out, int trajectory, T* u_out, void* stream) {                               \
+    RBD_ENTER rollout_cl_launch<T>(q0, qd0, u, k, K, q0_ref, qd0_ref, q_ref, qd_ref, alpha, u_lo, u_hi, dt, gravity, integrator, \
+                                   B, B_nom, steps, q_out, qd_out, trajectory, u_out, stream);                                   \
+  }
+#define RBD_STUBS_ROLLCL(SFX, T)                                                                                                 \
+  int rbd_rollout_closed_loop_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*,    \
+                                    const T*, const T*, const T*, T, T, int, int64_t, int64_t, int64_t, T*, T*, int, T*, void*)  \
+      RBD_STUB_BODY("rbd_rollout_closed_loop")
+
+#define RBD_DEFS_ROLLG(SFX, T)                                                                                                \
   int rbd_rollout_adjoint_##SFX(const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator, \
                                 int64_t B, int64_t steps, T* lam, T* grad_u, void* stream) {                                     \
     RBD_ENTER rollout_adjoint_launch<T>(dc_du, Minv, gq, gqd, g_final_only, dt, integrator, B, steps, lam, grad_u, stream);      \
@@ -1318,6 +1369,17 @@ RBD_STUBS_ROLL(f32, float)
 RBD_DEFS_ROLL(f64, double)
 #elif defined(RBD_STUB_ROLL_F64)
 RBD_STUBS_ROLL(f64, double)
+#endif
+
+#if defined(RBD_TU_ROLLCL_F32)
+RBD_DEFS_ROLLCL(f32, float)
+#elif defined(RBD_STUB_ROLLCL_F32)
+RBD_STUBS_ROLLCL(f32, float)
+#endif
+#if defined(RBD_TU_ROLLCL_F64)
+RBD_DEFS_ROLLCL(f64, double)
+#elif defined(RBD_STUB_ROLLCL_F64)
+RBD_STUBS_ROLLCL(f64, double)
 #endif
 
 #if defined(RBD_TU_ROLLG_F32)

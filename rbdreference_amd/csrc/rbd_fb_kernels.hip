@@ -364,6 +364,11 @@ RBD_DECLS_SELECTION(f64)
   int rbd_rollout_##SFX(const T*, const T*, const T*, int, T, T, int, int64_t, int64_t, T*, T*, int, void*) {              \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout: fixed-base robots only (a floating base needs an integrator on SE(3))"); \
   }                                                                                                                         \
+  int rbd_rollout_closed_loop_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*,         \
+                                    const T*, const T*, const T*, const T*, T, T, int, int64_t, int64_t, int64_t, T*, T*,   \
+                                    int, T*, void*) {                                                                       \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_closed_loop: fixed-base robots only (rbd_rollout has no floating base)"); \
+  }                                                                                                                         \
   int rbd_rollout_adjoint_##SFX(const T*, const T*, const T*, const T*, int, T, int, int64_t, int64_t, T*, T*, void*) {    \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_adjoint: fixed-base robots only (rbd_rollout has no floating base)");    \
   }                                                                                                                         \
