@@ -485,6 +485,50 @@ int rbd_rollout_closed_loop_f64(const double* q0, const double* qd0, const doubl
                                 int integrator, int64_t B, int64_t B_nom, int64_t T, double* q_out, double* qd_out,
                                 int trajectory, double* u_out, void* stream);
 
+/* Rollout with its cost: rbd_rollout_closed_loop's time loop, open or closed loop, with a quadratic tracking cost accumulated
+ * inside it -- the line search of iLQR / DDP, the sample costs of a sampling controller -- in ONE launch that writes cost [B]
+ * and nothing else unless asked.  Fixed base only; a floating-base library returns RBD_ERR_UNSUPPORTED.  Conventions, the
+ * shared nominal (row r reads row r % B_nom) and the integrators are rbd_rollout_closed_loop's.  Per row and step:
+ *   u_t = u[t] + alpha k[t], then + du[t], then + K[t] dx (the 2n products in order), then the limits
+ *         (one chain per joint; k, du, K and the limits are each optional; K == NULL is an OPEN loop and the four reference
+ *         pointers are not read)
+ *   qdd = aba(q_t, qd_t, u_t, gravity), then the integrator's two fused multiply-adds
+ *   J  += sum_j 1/2 w_u[t,j] u_t,j^2 + c_u[t,j] u_t,j                                    (u_t: the control applied, after limits)
+ *       + sum_j 1/2 w_q[t,j] (q_{t+1,j} - q_tgt[t,j])^2 + sum_j 1/2 w_qd[t,j] (qd_{t+1,j} - qd_tgt[t,j])^2
+ * J is ONE chain per row in a fixed order, in the kernel's precision: for t = 0 .. T - 1 the control terms j = 0 .. n - 1 (per
+ * joint fma((w_u / 2 * u), u, J), then fma(c_u, u, J)), then the q terms j = 0 .. n - 1 (d = q - q_tgt; fma((w_q / 2 * d), d, J)),
+ * then the qd terms.  A row's J depends on that row's values alone: not on B, B_nom, its lane or block, nor on which optional
+ * outputs are stored.
+ *   q0, qd0            : [B, n] device; never written
+ *   u                  : [T, B_nom, n]
+ *   k, alpha           : [T, B_nom, n] and [B], or both NULL
+ *   K                  : [T, B_nom, n, 2n], or NULL (open loop)
+ *   q0_ref, qd0_ref, q_ref, qd_ref : as rbd_rollout_closed_loop; required when K is given, ignored otherwise
+ *   du                 : [T, B, n], a perturbation of the control per ROW, or NULL
+ *   u_lo, u_hi         : [n] device, or both NULL
+ *   q_tgt, qd_tgt, w_q, w_qd : x_final_only == 0: [T, B_nom, n]; x_final_only != 0: [B_nom, n], a cost on slice T - 1 alone.
+ *                        Any may be NULL: a NULL weight drops its term, a NULL target is zero
+ *   w_u, c_u           : [T, B_nom, n]; a NULL w_u drops the quadratic term, a NULL c_u the linear one
+ *   cost               : [B], always written
+ *   q_out, qd_out      : both or neither; trajectory != 0: [T, B, n]; trajectory == 0: [B, n], the final state.  NULL: not stored
+ *   u_out              : [T, B, n], the controls applied, or NULL
+ * Arguments are checked before anything touches the GPU: NULL q0, qd0, u or cost, K with a NULL reference pointer, k xor alpha
+ * NULL, u_lo xor u_hi NULL, q_out xor qd_out NULL, B < 0, T < 0, B > 0 with B_nom <= 0 or B not a multiple of B_nom, dt not
+ * finite, unknown integrator, misaligned output, B or B T n or B_nom T n 2n too large: RBD_ERR_ARG; a robot whose state exceeds
+ * the LDS: RBD_ERR_UNSUPPORTED.  B == 0 or T == 0 is a no-op: nothing is written. */
+int rbd_rollout_cost_f32(const float* q0, const float* qd0, const float* u, const float* k, const float* K,
+                         const float* q0_ref, const float* qd0_ref, const float* q_ref, const float* qd_ref,
+                         const float* alpha, const float* du, const float* u_lo, const float* u_hi, const float* q_tgt,
+                         const float* qd_tgt, const float* w_q, const float* w_qd, int x_final_only, const float* w_u,
+                         const float* c_u, float dt, float gravity, int integrator, int64_t B, int64_t B_nom, int64_t T,
+                         float* cost, float* q_out, float* qd_out, int trajectory, float* u_out, void* stream);
+int rbd_rollout_cost_f64(const double* q0, const double* qd0, const double* u, const double* k, const double* K,
+                         const double* q0_ref, const double* qd0_ref, const double* q_ref, const double* qd_ref,
+                         const double* alpha, const double* du, const double* u_lo, const double* u_hi, const double* q_tgt,
+                         const double* qd_tgt, const double* w_q, const double* w_qd, int x_final_only, const double* w_u,
+                         const double* c_u, double dt, double gravity, int integrator, int64_t B, int64_t B_nom, int64_t T,
+                         double* cost, double* q_out, double* qd_out, int trajectory, double* u_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "rbd_rollout_riccati_f32", "rbd_rollout_riccati_f64",
     "rbd_rollout_lqr_workspace_bytes", "rbd_rollout_lqr_f32", "rbd_rollout_lqr_f64",
     "rbd_rollout_closed_loop_f32", "rbd_rollout_closed_loop_f64",
+    "rbd_rollout_cost_f32", "rbd_rollout_cost_f64",
 ]
 RBD_EE_MAX_SITES = 16
 
@@ -156,6 +157,10 @@ def _declare(lib):
         f = getattr(lib, f"rbd_rollout_closed_loop_{sfx}")
         f.restype = c_int
         f.argtypes = [*[c_void_p] * 12, ct, ct, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+        f = getattr(lib, f"rbd_rollout_cost_{sfx}")
+        f.restype = c_int
+        f.argtypes = [*[c_void_p] * 17, c_int, c_void_p, c_void_p, ct, ct, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                      c_void_p, c_int, c_void_p, c_void_p]
     lib.rbd_rollout_lqr_workspace_bytes.restype = c_size_t
     lib.rbd_rollout_lqr_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_rollout_grad_workspace_bytes.restype = c_size_t

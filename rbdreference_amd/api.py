@@ -14,6 +14,7 @@ import contextlib
 import os
 import threading
 from sys import getrefcount as _refs
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -43,6 +44,11 @@ _tid = threading.get_ident
 POOL_SETS = 3
 POOL_MAX_BYTES = 160 << 20
 POOL_SIGNATURES = 16
+
+
+_COST_ARRAYS = ("w_q", "w_qd", "q_target", "qd_target", "w_u", "c_u")      # QuadraticCost's arrays, in its constructor's order
+# what RBDReference.ilqr returns: the final nominal and the per-iteration record
+IlqrResult = namedtuple("IlqrResult", ["u", "q", "qd", "cost", "alpha", "dV", "status"])
 
 
 class _OutSet:
@@ -936,9 +942,21 @@ class RBDReference:
             q, qd = q.squeeze(-2), qd.squeeze(-2)
         return (q.cpu().numpy(), qd.cpu().numpy()) if is_np else (q, qd)
 
+    @staticmethod
+    def _check_row_alpha(who, row_alpha, alpha, k, lead):
+        """``row_alpha``: one step size per row, instead of ``alpha`` (which must keep its default) and with ``k``."""
+        if row_alpha is None:
+            return
+        if np.shape(alpha) != () or isinstance(alpha, torch.Tensor) or float(alpha) != 1.0:
+            raise ValueError(f"{who}: give alpha or row_alpha, not both")
+        if k is None:
+            raise ValueError(f"{who}: row_alpha scales k, which is missing")
+        if tuple(np.shape(row_alpha)) != tuple(lead):
+            raise ValueError(f"{who}: row_alpha must be {list(lead)} (one step size per row), got {tuple(np.shape(row_alpha))}")
+
     # ---- closed-loop rollouts: rbd_rollout_closed_loop, the control law u = u + alpha k + K dx inside the time loop ----
     def rollout_closed_loop(self, q0, qd0, u, q_ref, qd_ref, K, dt, k=None, alpha=1.0, q0_ref=None, qd0_ref=None,
-                            u_min=None, u_max=None, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True):
+                            u_min=None, u_max=None, GRAVITY=-9.81, integrator="semi_implicit", trajectory=True, row_alpha=None):
         """The forward pass that consumes ``rollout_lqr``'s gains, in ONE kernel launch -> ``(q, qd, u_applied)``: an
         iLQR / DDP line search, a time-varying LQR tracking controller, roll-outs around a feedback policy.  Not part of
         the reference.  With ``x = (q | qd)``, per row and step
@@ -957,8 +975,10 @@ class RBDReference:
         ``trajectory=False``; ``u_applied``, the controls actually applied, is ``[T, B, n]`` either way).  A 1-D ``alpha``
         of length ``A`` (sequence, array or tensor) is a line search: ``A B`` rows run against the one nominal -- every
         candidate shares its ``K`` stream -- and the outputs are ``[T, A, B, n]`` (final state ``[A, B, n]``).  Unbatched
-        inputs (``q0 [n]``, ``u [T, n]``, ``K [T, n, 2n]``) drop the ``B`` axis.  numpy in -> float64 numpy out; tensors
-        stay on their device and dtype and run on torch's current stream.  Fixed-base robots only."""
+        inputs (``q0 [n]``, ``u [T, n]``, ``K [T, n, 2n]``) drop the ``B`` axis.  ``row_alpha [B]`` gives every row its own
+        step size instead (it needs ``k`` and the default ``alpha``): the forward pass of an optimiser that accepts or
+        rejects per row.  numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's
+        current stream.  Fixed-base robots only."""
         from ._lib import RBD_INTEGRATORS
         who = "rollout_closed_loop"
         if self.model.floating:
@@ -997,6 +1017,7 @@ class RBDReference:
         if len(sa) > 1 or (len(sa) == 1 and sa[0] == 0):
             raise ValueError(f"{who}: alpha must be a float or a non-empty 1-D sequence of step sizes, got shape {sa}")
         A = sa[0] if sa else None
+        self._check_row_alpha(who, row_alpha, alpha, k, lead)
         (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
 
         def dev_of(x, dtype=None):
@@ -1023,7 +1044,9 @@ class RBDReference:
             if A is not None:
                 q0, qd0 = q0.repeat(A, 1), qd0.repeat(A, 1)          # row a B + b starts where row b does
             al = None
-            if k is not None:
+            if row_alpha is not None:
+                al = dev_of(row_alpha).reshape(rows)
+            elif k is not None:
                 if A is None:
                     al = torch.full((rows,), float(alpha), device=dev, dtype=dtp)
                 else:
@@ -1045,6 +1068,233 @@ class RBDReference:
                 x = x.squeeze(-2)
             outs.append(x.cpu().numpy() if is_np else x)
         return tuple(outs)
+
+    # ---- rollouts that return their cost: rbd_rollout_cost, the quadratic cost accumulated inside the time loop ----------
+    def rollout_cost(self, q0, qd0, u, dt, cost, K=None, q_ref=None, qd_ref=None, k=None, alpha=1.0, du=None, q0_ref=None,
+                     qd0_ref=None, u_min=None, u_max=None, GRAVITY=-9.81, integrator="semi_implicit", row_alpha=None,
+                     return_final=False, return_trajectory=False):
+        """A rollout, open or closed loop, that returns its cost ``J [B]`` and stores nothing else: the line search of
+        iLQR / DDP and the sample costs of a sampling controller (MPPI) in ONE kernel launch.  Not part of the reference.
+        ``cost`` is a ``QuadraticCost``; per row and step
+
+            ``u_t = u[t] + alpha k[t] + du[t] + K[t] dx`` (``rollout_closed_loop``'s control law; ``k``, ``du`` and ``K`` are
+            each optional), clipped to ``[u_min, u_max]`` when limits are given;  the state advances as in ``rollout``;
+            ``J += 1/2 w_u u_t^2 + c_u u_t + 1/2 w_q (q_{t+1} - q_target)^2 + 1/2 w_qd (qd_{t+1} - qd_target)^2`` summed
+            over the joints, with ``u_t`` the control applied and slice ``t`` the state after step ``t``
+
+        accumulated in the kernel's precision as one chain per row in a fixed order (per step: the control terms joint
+        by joint, then the ``q`` terms, then the ``qd`` terms), so a row's ``J`` depends on that row alone.
+
+        Time-major like ``rollout``: ``q0, qd0 [B, n]``; ``u [T, B_nom, n]`` where ``B_nom`` divides ``B`` (``B_nom = 1``:
+        one nominal shared by ``B`` samples); ``K [T, B_nom, n, 2n]`` or ``None`` -- an OPEN loop, in which ``q_ref, qd_ref,
+        q0_ref, qd0_ref`` are not used; with ``K``, ``q_ref, qd_ref [T, B_nom, n]`` are required and ``q0_ref, qd0_ref
+        [B_nom, n]`` default to ``q0, qd0`` (``B_nom = B`` only).  ``k [T, B_nom, n]``; ``du [T, B, n]``, a perturbation per
+        ROW.  The cost's arrays belong to the nominal (``B_nom`` rows).  A float ``alpha`` gives ``J [B]``; a 1-D
+        ``alpha`` of length ``A`` runs ``A B`` rows against the one nominal and gives ``J [A, B]`` (``du`` is then
+        ``[T, A, B, n]``); ``row_alpha [B]`` gives every row its own step size instead.  ``return_final=True`` ->
+        ``(J, q_T, qd_T)``; ``return_trajectory=True`` -> ``(J, q, qd, u_applied)`` with ``rollout_closed_loop``'s shapes (one
+        of the two, not both).
+        numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
+
+        Robots with PRISMATIC joints: nothing here differentiates, but gains that come from ``rollout_lqr`` inherit its
+        caveat (``rnea_grad``'s ``dc_dq`` is not the q-derivative for such joints).  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        from .cost import QuadraticCost
+        who = "rollout_cost"
+        if self.model.floating:
+            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        if not isinstance(cost, QuadraticCost):
+            raise TypeError(f"{who}: cost must be a QuadraticCost")
+        if return_final and return_trajectory:
+            raise ValueError(f"{who}: give return_final or return_trajectory, not both (the final state is the trajectory's last slice)")
+        n = self.n
+        sq = tuple(np.shape(q0))                  # shapes first: refused before anything touches the GPU
+        if len(sq) != 2 or sq[1] != n or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"{who}: q0 and qd0 must both be [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        B = sq[0]
+        su = tuple(np.shape(u))
+        if len(su) != 3 or su[2] != n or su[1] == 0 or B % su[1] != 0:
+            raise ValueError(f"{who}: u must be [T, B_nom, {n}] (time-major) with B_nom dividing B = {B}, got {su}")
+        T, Bn = su[0], su[1]
+        if T == 0:
+            raise ValueError(f"{who}: u holds no step (T == 0)")
+        if K is None:
+            if any(x is not None for x in (q_ref, qd_ref, q0_ref, qd0_ref)):
+                raise ValueError(f"{who}: q_ref, qd_ref, q0_ref and qd0_ref belong to the feedback term; K is missing")
+        else:
+            if q_ref is None or qd_ref is None:
+                raise ValueError(f"{who}: K needs q_ref and qd_ref (the nominal trajectory)")
+            if (q0_ref is None) != (qd0_ref is None):
+                raise ValueError(f"{who}: give q0_ref and qd0_ref together, or neither (they default to q0, qd0)")
+            if q0_ref is None and Bn != B:
+                raise ValueError(f"{who}: a nominal of {Bn} rows against {B} rows needs q0_ref and qd0_ref [{Bn}, {n}]")
+        sa = tuple(np.shape(alpha))
+        if len(sa) > 1 or (len(sa) == 1 and sa[0] == 0):
+            raise ValueError(f"{who}: alpha must be a float or a non-empty 1-D sequence of step sizes, got shape {sa}")
+        A = sa[0] if sa else None
+        self._check_row_alpha(who, row_alpha, alpha, k, (B,))
+        if A is not None and Bn != B:
+            raise ValueError(f"{who}: a 1-D alpha shares one nominal of B rows among its candidates; u has {Bn} rows, q0 {B}")
+        lead_du = (T,) + (() if A is None else (A,)) + (B, n)
+        for name, x, want in (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
+                              ("q0_ref", q0_ref, (Bn, n)), ("qd0_ref", qd0_ref, (Bn, n)), ("du", du, lead_du)):
+            if x is not None and tuple(np.shape(x)) != want:
+                raise ValueError(f"{who}: {name} must be {list(want)}, got {tuple(np.shape(x))}")
+        if (u_min is None) != (u_max is None):
+            raise ValueError(f"{who}: give u_min and u_max together, or neither")
+        for name, x in (("u_min", u_min), ("u_max", u_max)):
+            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
+                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
+        cd = cost.dense(T, Bn, n)                 # (raises on a shape that is none of the accepted forms)
+        (q0, qd0), _, is_np, dev, dtp = self._prep(q0, qd0)
+
+        def dev_of(x):
+            if x is None:
+                return None
+            if isinstance(x, torch.Tensor):
+                if is_np:
+                    raise TypeError("mixing numpy and torch inputs is not supported")
+                if x.device != dev or x.dtype != dtp:
+                    raise TypeError("all inputs must share device and dtype")
+                return x.contiguous()
+            if not is_np:
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
+
+        u, q_ref, qd_ref, K, k, du = (dev_of(x) for x in (u, q_ref, qd_ref, K, k, du))
+        cd = {name: dev_of(x) for name, x in cd.items()}
+        if K is not None:
+            q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (dev_of(q0_ref), dev_of(qd0_ref))
+        store = "trajectory" if return_trajectory else "final" if return_final else None
+        with torch.cuda.device(dev):
+            lims = [None, None]
+            if u_min is not None:
+                for i, x in enumerate((u_min, u_max)):
+                    x = x.to(device=dev, dtype=dtp) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
+                    lims[i] = x.expand(n).contiguous()
+            rows = B * (A or 1)
+            if A is not None:
+                q0, qd0 = q0.repeat(A, 1), qd0.repeat(A, 1)          # row a B + b starts where row b does
+            al = None
+            if row_alpha is not None:
+                al = dev_of(row_alpha)
+            elif k is not None:
+                if A is None:
+                    al = torch.full((rows,), float(alpha), device=dev, dtype=dtp)
+                else:
+                    a1 = alpha.to(device=dev, dtype=dtp) if isinstance(alpha, torch.Tensor) else torch.as_tensor(np.asarray(alpha, dtype=np.float64), device=dev).to(dtp)
+                    al = a1.repeat_interleave(B).contiguous()
+            J = torch.empty((rows,), device=dev, dtype=dtp)
+            q = qd = ua = None
+            if store is not None:
+                q = torch.empty((T, rows, n) if store == "trajectory" else (rows, n), device=dev, dtype=dtp)
+                qd = torch.empty_like(q)
+            if store == "trajectory":
+                ua = torch.empty((T, rows, n), device=dev, dtype=dtp)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._lib.check(self._fn("rbd_rollout_cost", dtp)(
+                self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(k), self._ptr(K), self._ptr(q0_ref), self._ptr(qd0_ref),
+                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(du), self._ptr(lims[0]), self._ptr(lims[1]),
+                self._ptr(cd["q_target"]), self._ptr(cd["qd_target"]), self._ptr(cd["w_q"]), self._ptr(cd["w_qd"]),
+                int(cost.terminal_state_only), self._ptr(cd["w_u"]), self._ptr(cd["c_u"]), float(dt), float(GRAVITY),
+                RBD_INTEGRATORS[integrator], rows, Bn, T, self._ptr(J), self._ptr(q), self._ptr(qd),
+                int(store == "trajectory"), self._ptr(ua), st))
+        outs = [J if A is None else J.view(A, B)]
+        for x in (q, qd, ua):
+            if x is not None:
+                outs.append(x if A is None else x.view(*x.shape[:-2], A, B, n))
+        if is_np:
+            outs = [x.cpu().numpy() for x in outs]
+        return outs[0] if store is None else tuple(outs)
+
+    # ---- iLQR: rollout_lqr -> rollout_cost (line search) -> rollout_closed_loop (forward pass), per-row accept / reject ----
+    def ilqr(self, q0, qd0, u, dt, cost, iters=10, alphas=(1, .5, .25, .125, .03125, .0078125), reg=0.0, u_min=None,
+             u_max=None, GRAVITY=-9.81, integrator="semi_implicit"):
+        """``iters`` iterations of iLQR on ``B`` independent problems -> ``IlqrResult(u, q, qd [T, B, n], cost [iters + 1, B],
+        alpha [iters, B], dV [iters, B, 2], status [iters, B])``.  Not part of the reference.  Per iteration, three
+        launches and some elementwise glue, with no host synchronisation:
+
+          1. ``cost.derivatives`` at the nominal and ``rollout_lqr(..., q=q, qd=qd, reg=reg)`` -> ``k, K, dV, status``;
+          2. ``rollout_cost`` over all ``alphas`` in one launch -> ``Jc [A, B]``; per row the lowest-index minimum, a NaN
+             counting as +inf; the row ACCEPTS when that minimum is below its current cost;
+          3. one ``rollout_closed_loop(row_alpha=...)`` with the accepted step sizes (0 for a rejected row); accepted rows
+             take the new ``u, q, qd`` and cost, rejected rows keep theirs (selected explicitly).
+
+        ``cost[i]`` is the cost entering iteration ``i`` (``cost[0]``: the start's, from an open-loop ``rollout_cost``), non-
+        increasing per row by construction; ``alpha`` records 0 for a rejected row; ``dV, status`` are ``rollout_lqr``'s.
+        ``q0, qd0 [B, n]``, ``u [T, B, n]``, ``cost``: a ``QuadraticCost``; ``reg``: a float or ``iters`` floats (one
+        regularisation for every row); ``u_min, u_max`` clip the controls applied (the backward pass does not know about
+        them).  numpy in -> float64 numpy out; tensors stay on their device and dtype.
+
+        Robots with PRISMATIC joints: ``rnea_grad``'s ``dc_dq`` reproduces the reference and is not the q-derivative for
+        such joints (see ``rollout_lqr``), so the gains are not those of the true linearisation there; the line search
+        still never accepts a step that raises the cost.  Fixed-base robots only."""
+        from .cost import QuadraticCost
+        who = "ilqr"
+        if self.model.floating:
+            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        if not isinstance(cost, QuadraticCost):
+            raise TypeError(f"{who}: cost must be a QuadraticCost")
+        n = self.n
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))
+        if len(sq) != 2 or sq[1] != n or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"{who}: q0 and qd0 must both be [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
+        if len(su) != 3 or su[1:] != sq or su[0] == 0:
+            raise ValueError(f"{who}: u must be [T, {sq[0]}, {n}] (time-major, T > 0), got {su}")
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"{who}: iters < 0")
+        if np.ndim(alphas) != 1 or len(alphas) == 0:
+            raise ValueError(f"{who}: alphas must be a non-empty 1-D sequence of step sizes")
+        regs = [float(reg)] * iters if np.ndim(reg) == 0 else [float(r) for r in reg]
+        if len(regs) != iters:
+            raise ValueError(f"{who}: reg must be a float or a sequence of iters = {iters} floats, got {len(regs)}")
+        is_np = not isinstance(q0, torch.Tensor)
+        if is_np:
+            if any(isinstance(x, torch.Tensor) for x in (qd0, u, *(getattr(cost, a) for a in _COST_ARRAYS))):
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            if not torch.cuda.is_available():
+                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
+            up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0")   # noqa: E731
+            q0, qd0, u = up(q0), up(qd0), up(u)
+            cost = QuadraticCost(*(up(getattr(cost, a)) for a in _COST_ARRAYS),
+                                 terminal_state_only=cost.terminal_state_only)
+        dev, dtp = q0.device, q0.dtype
+        kw = dict(GRAVITY=GRAVITY, integrator=integrator)
+        lim = dict(u_min=u_min, u_max=u_max)
+        with torch.cuda.device(dev):
+            al = torch.as_tensor(np.asarray(alphas, dtype=np.float64), device=dev).to(dtp)      # made once, before the loop
+            A = al.shape[0]
+            first = torch.arange(A, 0, -1, device=dev)[:, None]       # weights that make the LOWEST index win a tie
+            inf = torch.full((), float("inf"), device=dev, dtype=dtp)
+            zero = torch.zeros((), device=dev, dtype=dtp)
+            J, q, qd, u = self.rollout_cost(q0, qd0, u, dt, cost, return_trajectory=True, **lim, **kw)
+            hist, h_al, h_dV, h_st = [J], [], [], []
+            for it in range(iters):
+                d = cost.derivatives(q, qd, u)
+                k, K, _, _, dV, status = self.rollout_lqr(q0, qd0, u, dt, reg=regs[it], q=q, qd=qd, **d, **kw)
+                Jc = self.rollout_cost(q0, qd0, u, dt, cost, K=K, q_ref=q, qd_ref=qd, k=k, alpha=al, **lim, **kw)
+                Jc = torch.where(torch.isnan(Jc), inf, Jc)
+                J_best = Jc.min(dim=0).values
+                idx = ((Jc == J_best[None]) * first).argmax(dim=0)
+                accept = J_best < J
+                ra = torch.where(accept, al[idx], zero)
+                qn, qdn, un = self.rollout_closed_loop(q0, qd0, u, q, qd, K, dt, k=k, row_alpha=ra, **lim, **kw)
+                sel = accept[None, :, None]
+                u, q, qd = torch.where(sel, un, u), torch.where(sel, qn, q), torch.where(sel, qdn, qd)
+                J = torch.where(accept, J_best, J)
+                hist.append(J)
+                h_al.append(ra)
+                h_dV.append(dV)
+                h_st.append(status)
+            B = sq[0]
+            res = IlqrResult(u, q, qd, torch.stack(hist),
+                             torch.stack(h_al) if iters else torch.empty((0, B), device=dev, dtype=dtp),
+                             torch.stack(h_dV) if iters else torch.empty((0, B, 2), device=dev, dtype=dtp),
+                             torch.stack(h_st) if iters else torch.empty((0, B), device=dev, dtype=torch.int32))
+        return IlqrResult(*(x.cpu().numpy() for x in res)) if is_np else res
 
     # ---- reverse-mode gradient of a rollout: rbd_rollout_grad (aba, rnea_grad, minv per chunk + one scan launch) ------
     _ROLLG_WS_CAP = 1 << 30

@@ -721,6 +721,48 @@ int rollout_cl_launch(const T* q0, const T* qd0, const T* u, const T* k, const T
 }
 #endif  // RBD_NEED_ROLLCL
 
+#ifdef RBD_NEED_ROLLCOST
+// rbd_rollout_cost: one launch for all T steps, the control law and the cost's accumulation inside the time loop
+// (rbd_rollout_cost.h).  Arguments are checked before the launch.
+template <class T>
+int rollout_cost_launch(const T* q0, const T* qd0, const T* u, const T* k, const T* K, const T* q0_ref, const T* qd0_ref,
+                        const T* q_ref, const T* qd_ref, const T* alpha, const T* du, const T* u_lo, const T* u_hi,
+                        const T* q_tgt, const T* qd_tgt, const T* w_q, const T* w_qd, int x_final_only, const T* w_u,
+                        const T* c_u, T dt, T gravity, int integrator, int64_t B, int64_t B_nom, int64_t steps, T* cost,
+                        T* q_out, T* qd_out, int trajectory, T* u_out, void* stream) {
+  using namespace rbdk;
+  const char* who = "rbd_rollout_cost";
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "%s: fixed-base robots only", who);
+  if (B < 0) return fail(RBD_ERR_ARG, "%s: B < 0", who);
+  if (steps < 0) return fail(RBD_ERR_ARG, "%s: T < 0", who);
+  if (!(dt - dt == T(0))) return fail(RBD_ERR_ARG, "%s: dt must be finite", who);
+  if (integrator != RBD_INTEGRATOR_SEMI_IMPLICIT && integrator != RBD_INTEGRATOR_EULER)
+    return fail(RBD_ERR_ARG, "%s: unknown integrator (0 = semi-implicit Euler, 1 = explicit Euler)", who);
+  if (B == 0 || steps == 0) return 0;
+  if (B_nom <= 0 || B % B_nom != 0) return fail(RBD_ERR_ARG, "%s: B_nom must be positive and divide B", who);
+  if (!q0 || !qd0 || !u || !cost) return fail(RBD_ERR_ARG, "%s: q0, qd0, u and cost must be non-null", who);
+  if (K && (!q0_ref || !qd0_ref || !q_ref || !qd_ref))
+    return fail(RBD_ERR_ARG, "%s: K needs q0_ref, qd0_ref, q_ref and qd_ref", who);
+  if ((k == nullptr) != (alpha == nullptr)) return fail(RBD_ERR_ARG, "%s: k and alpha must be both null or both non-null", who);
+  if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(RBD_ERR_ARG, "%s: u_lo and u_hi must be both null or both non-null", who);
+  if ((q_out == nullptr) != (qd_out == nullptr)) return fail(RBD_ERR_ARG, "%s: q_out and qd_out must be both null or both non-null", who);
+  if (misaligned(cost, q_out, qd_out, u_out)) return fail(RBD_ERR_ARG, "%s: output buffers must be 16-byte aligned", who);
+  unsigned grid;
+  if (int rc = grid_for(B, ABA_PARK ? rollcl_lanes<T>() : 64, who, &grid)) return rc;
+  // B T n elements of du and of each trajectory, B_nom T n 2n of K: byte offsets stay far inside int64
+  if (steps > (INT64_MAX / 64) / (B * N)) return fail(RBD_ERR_ARG, "%s: B * T * n too large", who);
+  if (steps > (INT64_MAX / 64) / (B_nom * N * 2 * N)) return fail(RBD_ERR_ARG, "%s: B_nom * T * n * 2n too large", who);
+  constexpr size_t lds = rollcl_lds_bytes<T>();
+  if (lds > LDS_MAX) return fail(RBD_ERR_UNSUPPORTED, "%s: per-body state does not fit LDS for this robot size", who);
+  const long long row = (long long)B * N;
+  const int aligned = (row * (long long)sizeof(T)) % 16 == 0;      // every trajectory slice starts on a 16-byte boundary
+  const RollCostModel<T> cm{q_tgt, qd_tgt, w_q, w_qd, w_u, c_u, x_final_only ? 1 : 0};
+  return launch("rbd_rollout_cost launch", rollout_cost_kernel<T>, grid, ROLLCL_THREADS, lds, stream, q0, qd0, u, k, K, q0_ref,
+                qd0_ref, q_ref, qd_ref, alpha, du, u_lo, u_hi, cm, dt, gravity, integrator, B, B_nom, steps, cost, q_out,
+                qd_out, trajectory ? 1 : 0, u_out, row, aligned);
+}
+#endif  // RBD_NEED_ROLLCOST
+
 // rbd_rollout_grad's workspace for chunks of Tc steps, R = Tc B flat rows: minv's scratch | qdd [R, N] | dc_du [R, N, 2N] |
 // Minv [R, N, N] | lam [B, 2N]
 #if defined(RBD_TU_COMMON) || defined(RBD_NEED_ROLLG)
@@ -1232,6 +1274,21 @@ RBD_DECLS_SELECTION(f64)
                                     const T*, const T*, const T*, T, T, int, int64_t, int64_t, int64_t, T*, T*, int, T*, void*)  \
       RBD_STUB_BODY("rbd_rollout_closed_loop")
 
+#define RBD_DEFS_ROLLCOST(SFX, T)                                                                                                \
+  int rbd_rollout_cost_##SFX(const T* q0, const T* qd0, const T* u, const T* k, const T* K, const T* q0_ref, const T* qd0_ref,   \
+                             const T* q_ref, const T* qd_ref, const T* alpha, const T* du, const T* u_lo, const T* u_hi,         \
+                             const T* q_tgt, const T* qd_tgt, const T* w_q, const T* w_qd, int x_final_only, const T* w_u,       \
+                             const T* c_u, T dt, T gravity, int integrator, int64_t B, int64_t B_nom, int64_t steps, T* cost,    \
+                             T* q_out, T* qd_out, int trajectory, T* u_out, void* stream) {                                      \
+    RBD_ENTER rollout_cost_launch<T>(q0, qd0, u, k, K, q0_ref, qd0_ref, q_ref, qd_ref, alpha, du, u_lo, u_hi, q_tgt, qd_tgt,     \
+                                     w_q, w_qd, x_final_only, w_u, c_u, dt, gravity, integrator, B, B_nom, steps, cost, q_out,   \
+                                     qd_out, trajectory, u_out, stream);                                                         \
+  }
+#define RBD_STUBS_ROLLCOST(SFX, T)                                                                                               \
+  int rbd_rollout_cost_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, \
+                             const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, const T*, const T*, T,   \
+                             T, int, int64_t, int64_t, int64_t, T*, T*, T*, int, T*, void*) RBD_STUB_BODY("rbd_rollout_cost")
+
 #define RBD_DEFS_ROLLG(SFX, T)                                                                                                \
   int rbd_rollout_adjoint_##SFX(const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator, \
                                 int64_t B, int64_t steps, T* lam, T* grad_u, void* stream) {                                     \
@@ -1380,6 +1437,17 @@ RBD_STUBS_ROLLCL(f32, float)
 RBD_DEFS_ROLLCL(f64, double)
 #elif defined(RBD_STUB_ROLLCL_F64)
 RBD_STUBS_ROLLCL(f64, double)
+#endif
+
+#if defined(RBD_TU_ROLLCOST_F32)
+RBD_DEFS_ROLLCOST(f32, float)
+#elif defined(RBD_STUB_ROLLCOST_F32)
+RBD_STUBS_ROLLCOST(f32, float)
+#endif
+#if defined(RBD_TU_ROLLCOST_F64)
+RBD_DEFS_ROLLCOST(f64, double)
+#elif defined(RBD_STUB_ROLLCOST_F64)
+RBD_STUBS_ROLLCOST(f64, double)
 #endif
 
 #if defined(RBD_TU_ROLLG_F32)

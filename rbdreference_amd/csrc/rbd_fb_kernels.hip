@@ -369,6 +369,11 @@ RBD_DECLS_SELECTION(f64)
                                     int, T*, void*) {                                                                       \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_closed_loop: fixed-base robots only (rbd_rollout has no floating base)"); \
   }                                                                                                                         \
+  int rbd_rollout_cost_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*,      \
+                             const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, const T*, \
+                             const T*, T, T, int, int64_t, int64_t, int64_t, T*, T*, T*, int, T*, void*) {                  \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_cost: fixed-base robots only (rbd_rollout has no floating base)");       \
+  }                                                                                                                         \
   int rbd_rollout_adjoint_##SFX(const T*, const T*, const T*, const T*, int, T, int, int64_t, int64_t, T*, T*, void*) {    \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_adjoint: fixed-base robots only (rbd_rollout has no floating base)");    \
   }                                                                                                                         \
