@@ -529,6 +529,47 @@ int rbd_rollout_cost_f64(const double* q0, const double* qd0, const double* u, c
                          const double* c_u, double dt, double gravity, int integrator, int64_t B, int64_t B_nom, int64_t T,
                          double* cost, double* q_out, double* qd_out, int trajectory, double* u_out, void* stream);
 
+/* The update of a sampling controller (MPPI) from the sample costs rbd_rollout_cost wrote: softmin weights and the weighted sum
+ * of the perturbations, du read once.  P independent problems (rbd_rollout_cost's B_nom rows), S samples each, in its row
+ * layout: row s P + p is sample s of problem p.  Fixed base only; a floating-base library returns RBD_ERR_UNSUPPORTED.  Per
+ * problem p, in the entry point's precision:
+ *   Jm  = min_s J[s,p]                                      (a NaN counts as +inf)
+ *   x_s = (J[s,p] - Jm) / lam[p];  e_s = exp(-x_s)          (1 at a minimum, 0 for a NaN or +inf sample)
+ *   eta = sum_s e_s;  w_s = e_s / eta;  ess = eta^2 / sum_s e_s^2
+ *   d_s[t,j] = du[t,s,p,j], or with limits clamp(u[t,p,j] + du[t,s,p,j], u_lo[j], u_hi[j]) - u[t,p,j]  (what rbd_rollout_cost
+ *              applied: u < lo ? lo : (u > hi ? hi : u))
+ *   u_out[t,p,j] = u[t,p,j] + (sum_s e_s d_s[t,j]) / eta, clamped once more when limits are given
+ *   status[p] = 2: lam[p] is not finite and positive; else 1: Jm is not finite (every sample NaN or +inf, or a -inf among
+ *               them); else 0.  Where it is not 0: u_out[:,p] = u[:,p] (clamped when limits are given), w = 0, ess = 0.
+ * Nothing else is special: a NaN in du poisons the (t, j) outputs of its own problem and no other.
+ * Summation order -- a function of S and RBD_MPPI_CHUNK alone, not of P, T or the optional outputs; no floating-point atomics.
+ * Each of eta, sum e^2 and sum e d[t,j]: per chunk of RBD_MPPI_CHUNK consecutive samples one chain from zero in ascending s
+ * (a += e; a = fma(e, e, a); a = fma(e, d, a)); then per group of RBD_MPPI_CHUNK consecutive chunks the chunks added in
+ * ascending order; then the groups added in ascending order.
+ *   J                  : [S, P] device; never written (as every input)
+ *   du                 : [T, S, P, n]
+ *   u                  : [T, P, n]
+ *   lam                : [P]
+ *   u_lo, u_hi         : [n] device, or both NULL
+ *   u_out              : [T, P, n]
+ *   w_out              : [S, P], or NULL
+ *   ess_out            : [P], or NULL
+ *   status_out         : [P] int32
+ *   ws, ws_bytes       : device scratch of at least rbd_mppi_update_workspace_bytes bytes (S, P, T, 4 or 8): e [S, P], eta [P]
+ *                        and, when S > RBD_MPPI_CHUNK, the chunk partials [ceil(S / RBD_MPPI_CHUNK), T, P, n].  The query
+ *                        returns 0 for a size that is not positive or too large, and on a floating-base library
+ * Arguments are checked before anything touches the GPU: NULL J, du, u, lam, u_out or status_out, u_lo xor u_hi NULL, S, P or
+ * T < 0, S P or T S P n too large, misaligned output or workspace: RBD_ERR_ARG; a workspace that is missing or too small:
+ * RBD_ERR_WORKSPACE.  S == 0, P == 0 or T == 0 is a no-op: nothing is written. */
+#define RBD_MPPI_CHUNK 64
+size_t rbd_mppi_update_workspace_bytes(int64_t S, int64_t P, int64_t T, int elem_size);
+int rbd_mppi_update_f32(const float* J, const float* du, const float* u, const float* lam, const float* u_lo, const float* u_hi,
+                        int64_t S, int64_t P, int64_t T, float* u_out, float* w_out, float* ess_out, int32_t* status_out,
+                        void* ws, size_t ws_bytes, void* stream);
+int rbd_mppi_update_f64(const double* J, const double* du, const double* u, const double* lam, const double* u_lo,
+                        const double* u_hi, int64_t S, int64_t P, int64_t T, double* u_out, double* w_out, double* ess_out,
+                        int32_t* status_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

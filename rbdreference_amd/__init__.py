@@ -9,7 +9,7 @@ from .robot import (BUILTIN_ROBOTS, FloatingBaseRobot, Link, Robot, atlas_like, 
 from .packer import PackedModel, pack_robot
 from .urdf import load_urdf, loads_urdf, to_urdf
 
-__all__ = ["RBDReference", "QuadraticCost", "IlqrResult", "Robot", "FloatingBaseRobot", "floating_quadruped_like", "Link", "iiwa_like",
+__all__ = ["RBDReference", "QuadraticCost", "IlqrResult", "MppiUpdate", "MppiResult", "Robot", "FloatingBaseRobot", "floating_quadruped_like", "Link", "iiwa_like",
            "quadruped_like", "atlas_like",
            "random_tree", "builtin_robot", "BUILTIN_ROBOTS", "pack_robot", "PackedModel",
            "load_urdf", "loads_urdf", "to_urdf"]
@@ -20,9 +20,9 @@ def __getattr__(name):
     if name == "RBDReference":
         from .api import RBDReference
         return RBDReference
-    if name == "IlqrResult":
-        from .api import IlqrResult
-        return IlqrResult
+    if name in ("IlqrResult", "MppiUpdate", "MppiResult"):
+        from . import api
+        return getattr(api, name)
     if name == "QuadraticCost":
         from .cost import QuadraticCost
         return QuadraticCost

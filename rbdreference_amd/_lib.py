@@ -51,7 +51,9 @@ EXPORTED_SYMBOLS = [
     "rbd_rollout_lqr_workspace_bytes", "rbd_rollout_lqr_f32", "rbd_rollout_lqr_f64",
     "rbd_rollout_closed_loop_f32", "rbd_rollout_closed_loop_f64",
     "rbd_rollout_cost_f32", "rbd_rollout_cost_f64",
+    "rbd_mppi_update_workspace_bytes", "rbd_mppi_update_f32", "rbd_mppi_update_f64",
 ]
+RBD_MPPI_CHUNK = 64         # samples per summation chunk of rbd_mppi_update (include/rbd_hip.h)
 RBD_EE_MAX_SITES = 16
 
 
@@ -161,6 +163,11 @@ def _declare(lib):
         f.restype = c_int
         f.argtypes = [*[c_void_p] * 17, c_int, c_void_p, c_void_p, ct, ct, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                       c_void_p, c_int, c_void_p, c_void_p]
+        f = getattr(lib, f"rbd_mppi_update_{sfx}")
+        f.restype = c_int
+        f.argtypes = [*[c_void_p] * 6, c_int64, c_int64, c_int64, *[c_void_p] * 5, c_size_t, c_void_p]
+    lib.rbd_mppi_update_workspace_bytes.restype = c_size_t
+    lib.rbd_mppi_update_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int]
     lib.rbd_rollout_lqr_workspace_bytes.restype = c_size_t
     lib.rbd_rollout_lqr_workspace_bytes.argtypes = [c_int64, c_int64, c_int]
     lib.rbd_rollout_grad_workspace_bytes.restype = c_size_t

@@ -49,6 +49,9 @@ POOL_SIGNATURES = 16
 _COST_ARRAYS = ("w_q", "w_qd", "q_target", "qd_target", "w_u", "c_u")      # QuadraticCost's arrays, in its constructor's order
 # what RBDReference.ilqr returns: the final nominal and the per-iteration record
 IlqrResult = namedtuple("IlqrResult", ["u", "q", "qd", "cost", "alpha", "dV", "status"])
+# what RBDReference.mppi_update and RBDReference.mppi return
+MppiUpdate = namedtuple("MppiUpdate", ["u", "w", "ess", "status"])
+MppiResult = namedtuple("MppiResult", ["u", "q", "qd", "cost", "ess", "status"])
 
 
 class _OutSet:
@@ -1295,6 +1298,188 @@ class RBDReference:
                              torch.stack(h_dV) if iters else torch.empty((0, B, 2), device=dev, dtype=dtp),
                              torch.stack(h_st) if iters else torch.empty((0, B), device=dev, dtype=torch.int32))
         return IlqrResult(*(x.cpu().numpy() for x in res)) if is_np else res
+
+    # ---- MPPI: rollout_cost (the sample costs) -> mppi_update (softmin weights, weighted sum of the perturbations) ----
+    @staticmethod
+    def _mppi_limits(who, u_min, u_max, n):
+        if (u_min is None) != (u_max is None):
+            raise ValueError(f"{who}: give u_min and u_max together, or neither")
+        for name, x in (("u_min", u_min), ("u_max", u_max)):
+            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
+                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
+
+    @staticmethod
+    def _mppi_small(x, dev, dtp):
+        """A float, sequence, array or tensor as a tensor of the call's device and dtype (lam, sigma, the limits)."""
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=dtp)
+        return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
+
+    def mppi_update(self, J, du, u, lam, u_min=None, u_max=None, return_weights=False):
+        """The update of a sampling controller from the sample costs ``rollout_cost`` wrote -> ``MppiUpdate(u, w, ess,
+        status)``.  Not part of the reference.  ``P`` independent problems with ``S`` samples each, in ``rollout_cost``'s
+        row layout (row ``s P + p`` is sample ``s`` of problem ``p``): ``J [S, P]``, ``du [T, S, P, n]``, ``u [T, P, n]``,
+        ``lam`` a float or ``[P]``.  Per problem, in the inputs' precision:
+
+            ``Jm = min_s J`` (a NaN counts as +inf);  ``e_s = exp(-(J_s - Jm) / lam)``;  ``eta = sum e``;  ``w = e / eta``;
+            ``ess = eta^2 / sum e^2``;  ``d_s = du_s``, or with limits ``clamp(u + du_s) - u`` -- the perturbation
+            ``rollout_cost`` applied;  ``u_new = u + (sum_s e_s d_s) / eta``, clamped once more when limits are given
+
+        ``status [P]`` (int32): 0; 1 when ``Jm`` is not finite (every sample NaN or +inf, or a -inf among them); 2 when
+        ``lam`` is not finite and positive.  Where it is not 0 the problem keeps its ``u`` (clamped), ``w = 0``, ``ess = 0``.
+        A NaN in ``du`` poisons the ``(t, j)`` outputs of its own problem and no other.  The sums run in a fixed order that
+        depends on ``S`` alone (chunks of ``RBD_MPPI_CHUNK`` samples), so a problem's result does not depend
+        on ``P``, ``T`` or ``return_weights``.  ``w [S, P]`` is ``None`` unless ``return_weights``.
+        numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
+        Fixed-base robots only."""
+        who = "mppi_update"
+        if self.model.floating:
+            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        n = self.n
+        sJ, sd, su = tuple(np.shape(J)), tuple(np.shape(du)), tuple(np.shape(u))
+        if len(sJ) != 2 or 0 in sJ:
+            raise ValueError(f"{who}: J must be [S, P] with S, P > 0, got {sJ}")
+        S, P = sJ
+        if len(su) != 3 or su[1:] != (P, n) or su[0] == 0:
+            raise ValueError(f"{who}: u must be [T, {P}, {n}] (time-major, T > 0), got {su}")
+        T = su[0]
+        if sd != (T, S, P, n):
+            raise ValueError(f"{who}: du must be {[T, S, P, n]}, got {sd}")
+        if tuple(np.shape(lam)) not in ((), (P,)):
+            raise ValueError(f"{who}: lam must be a float or [{P}], got shape {tuple(np.shape(lam))}")
+        self._mppi_limits(who, u_min, u_max, n)
+        is_np = not isinstance(J, torch.Tensor)
+        if any(isinstance(x, torch.Tensor) == is_np for x in (du, u)):
+            raise TypeError("mixing numpy and torch inputs is not supported")
+        if is_np:
+            if not torch.cuda.is_available():
+                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
+            J, du, u = (torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0") for x in (J, du, u))
+        dev, dtp = J.device, J.dtype
+        if dev.type != "cuda":
+            raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
+        if dtp not in (_F32, _F64):
+            raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
+        if any(x.device != dev or x.dtype != dtp for x in (du, u)):
+            raise TypeError("all inputs must share device and dtype")
+        esz = 4 if dtp == _F32 else 8
+        sfx = "f32" if esz == 4 else "f64"
+        with torch.cuda.device(dev):
+            J, du, u = J.contiguous(), du.contiguous(), u.contiguous()
+            lam_t = self._mppi_small(lam, dev, dtp).expand(P).contiguous()
+            lo = hi = None
+            if u_min is not None:
+                lo, hi = (self._mppi_small(x, dev, dtp).expand(n).contiguous() for x in (u_min, u_max))
+            u_new = torch.empty((T, P, n), device=dev, dtype=dtp)
+            w = torch.empty((S, P), device=dev, dtype=dtp) if return_weights else None
+            ess = torch.empty((P,), device=dev, dtype=dtp)
+            status = torch.empty((P,), device=dev, dtype=torch.int32)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib = self._lib.resolve("rbd_mppi_update", sfx)     # ONE resolution: workspace size and entry point from the same library
+            wsb = int(lib.rbd_mppi_update_workspace_bytes(S, P, T, esz))
+            ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
+            self._lib.check(getattr(lib, f"rbd_mppi_update_{sfx}")(
+                self._ptr(J), self._ptr(du), self._ptr(u), self._ptr(lam_t), self._ptr(lo), self._ptr(hi), S, P, T, self._ptr(u_new),
+                self._ptr(w), self._ptr(ess), self._ptr(status), ws.data_ptr(), wsb, st))
+        res = MppiUpdate(u_new, w, ess, status)
+        return MppiUpdate(*(None if x is None else x.cpu().numpy() for x in res)) if is_np else res
+
+    def mppi(self, q0, qd0, u, dt, cost, iters=1, samples=1024, sigma=0.1, lam=1.0, noise=None, generator=None, u_min=None,
+             u_max=None, GRAVITY=-9.81, integrator="semi_implicit"):
+        """``iters`` iterations of MPPI on ``P`` independent problems -> ``MppiResult(u, q, qd [T, P, n], cost [iters + 1, P],
+        ess [iters, P], status [iters, P])``.  Not part of the reference.  Per iteration, with ``S = samples``:
+
+          1. the noise ``eps [T, S, P, n]``: ``torch.randn(..., generator=generator)``, or ``noise[i]`` when ``noise [iters, T,
+             S, P, n]`` is given (``S`` is then its third extent);  ``du = sigma eps`` with ``du[:, 0] = 0`` -- sample 0 is
+             always the nominal, so its cost is the nominal's and needs no launch of its own;
+          2. one ``rollout_cost`` of the ``S P`` rows against the ``P`` nominals -> ``J [S, P]``;
+          3. one ``mppi_update`` -> the new ``u``, ``ess``, ``status``
+
+        with no host synchronisation.  ``cost[i] = J[0]`` of iteration ``i``, the cost of the nominal entering it; after
+        the loop one open-loop ``rollout_cost(return_trajectory=True)`` gives ``q, qd`` and ``cost[iters]``.
+        ``q0, qd0 [P, n]``, ``u [T, P, n]``, ``cost``: a ``QuadraticCost``; ``sigma``: a float, ``[n]`` or ``[T, n]``; ``lam``:
+        a float or ``[P]``; ``u_min, u_max`` clip the controls applied, and the update averages the clipped perturbations.
+        MPPI's control-cost coupling ``lam ubar^T Sigma^-1 du`` is expressed through ``QuadraticCost``'s ``c_u`` (``c_u =
+        lam ubar / sigma^2`` per step and joint): ``c_u (ubar + du)`` differs from it by ``c_u ubar``, a constant per
+        problem, which the softmin does not see.  Not included: shifting the nominal between the steps of a receding
+        horizon, and feedback gains around the samples.
+        numpy in -> float64 numpy out; tensors stay on their device and dtype.  Fixed-base robots only."""
+        from ._lib import RBD_INTEGRATORS
+        from .cost import QuadraticCost
+        who = "mppi"
+        if self.model.floating:
+            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        if integrator not in RBD_INTEGRATORS:
+            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        if not isinstance(cost, QuadraticCost):
+            raise TypeError(f"{who}: cost must be a QuadraticCost")
+        n = self.n
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))
+        if len(sq) != 2 or sq[1] != n or sq[0] == 0 or tuple(np.shape(qd0)) != sq:
+            raise ValueError(f"{who}: q0 and qd0 must both be [P, {n}] with P > 0, got {sq} and {tuple(np.shape(qd0))}")
+        if len(su) != 3 or su[1:] != sq or su[0] == 0:
+            raise ValueError(f"{who}: u must be [T, {sq[0]}, {n}] (time-major, T > 0), got {su}")
+        T, P = su[0], sq[0]
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"{who}: iters < 0")
+        if noise is not None:
+            if generator is not None:
+                raise ValueError(f"{who}: give noise or generator, not both")
+            sn = tuple(np.shape(noise))
+            if len(sn) != 5 or sn[:2] != (iters, T) or sn[3:] != (P, n) or sn[2] == 0:
+                raise ValueError(f"{who}: noise must be [iters = {iters}, {T}, S, {P}, {n}] with S > 0, got {sn}")
+            S = sn[2]
+        else:
+            S = int(samples)
+            if S < 1:
+                raise ValueError(f"{who}: samples < 1")
+        if tuple(np.shape(sigma)) not in ((), (n,), (T, n)):
+            raise ValueError(f"{who}: sigma must be a float, [{n}] or [{T}, {n}], got shape {tuple(np.shape(sigma))}")
+        if tuple(np.shape(lam)) not in ((), (P,)):
+            raise ValueError(f"{who}: lam must be a float or [{P}], got shape {tuple(np.shape(lam))}")
+        self._mppi_limits(who, u_min, u_max, n)
+        is_np = not isinstance(q0, torch.Tensor)
+        others = (qd0, u, *(getattr(cost, a) for a in _COST_ARRAYS)) + (() if noise is None else (noise,))
+        if is_np:
+            if any(isinstance(x, torch.Tensor) for x in others):
+                raise TypeError("mixing numpy and torch inputs is not supported")
+            if not torch.cuda.is_available():
+                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
+            up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0")   # noqa: E731
+            q0, qd0, u, noise = up(q0), up(qd0), up(u), up(noise)
+            cost = QuadraticCost(*(up(getattr(cost, a)) for a in _COST_ARRAYS),
+                                 terminal_state_only=cost.terminal_state_only)
+        elif not all(isinstance(x, torch.Tensor) for x in (qd0, u) + (() if noise is None else (noise,))):
+            raise TypeError("mixing numpy and torch inputs is not supported")
+        dev, dtp = q0.device, q0.dtype
+        kw = dict(GRAVITY=GRAVITY, integrator=integrator)
+        with torch.cuda.device(dev):
+            lim = dict(u_min=None, u_max=None)                         # the small tensors are made once, before the loop
+            if u_min is not None:
+                lim = dict(u_min=self._mppi_small(u_min, dev, dtp).expand(n).contiguous(), u_max=self._mppi_small(u_max, dev, dtp).expand(n).contiguous())
+            sg = self._mppi_small(sigma, dev, dtp)
+            if sg.dim() == 2:
+                sg = sg[:, None, None, :]
+            lam_t = self._mppi_small(lam, dev, dtp).expand(P).contiguous()
+            q0s, qd0s = q0.repeat(S, 1), qd0.repeat(S, 1)              # row s P + p starts where problem p does
+            hist, h_ess, h_st = [], [], []
+            for it in range(iters):
+                eps = noise[it] if noise is not None else torch.randn((T, S, P, n), generator=generator, device=dev, dtype=dtp)
+                du = sg * eps
+                du[:, 0] = 0
+                J = self.rollout_cost(q0s, qd0s, u, dt, cost, du=du.view(T, S * P, n), **lim, **kw).view(S, P)
+                upd = self.mppi_update(J, du, u, lam_t, **lim)
+                u = upd.u
+                hist.append(J[0])
+                h_ess.append(upd.ess)
+                h_st.append(upd.status)
+            Jf, q, qd, _ = self.rollout_cost(q0, qd0, u, dt, cost, return_trajectory=True, **lim, **kw)
+            hist.append(Jf)
+            res = MppiResult(u, q, qd, torch.stack(hist),
+                             torch.stack(h_ess) if iters else torch.empty((0, P), device=dev, dtype=dtp),
+                             torch.stack(h_st) if iters else torch.empty((0, P), device=dev, dtype=torch.int32))
+        return MppiResult(*(x.cpu().numpy() for x in res)) if is_np else res
 
     # ---- reverse-mode gradient of a rollout: rbd_rollout_grad (aba, rnea_grad, minv per chunk + one scan launch) ------
     _ROLLG_WS_CAP = 1 << 30

@@ -66,7 +66,8 @@ def _sources_digest(m: PackedModel, flags) -> str:
 TRANSLATION_UNITS = ["COMMON", "RNEA_F32", "RNEA_F64", "GRAD_F32", "GRAD_F64", "GRADN_F32", "GRADN_F64", "MINV_F32", "MINV_F64",
                      "FD_F32", "FD_F64", "PASS_F32", "PASS_F64", "EE_F32", "EE_F64",
                      "SO_F32", "SO_F64", "FDSO_F32", "FDSO_F64", "ROLL_F32", "ROLL_F64", "ROLLG_F32", "ROLLG_F64",
-                     "LQR_F32", "LQR_F64", "ROLLCL_F32", "ROLLCL_F64", "ROLLCOST_F32", "ROLLCOST_F64"]
+                     "LQR_F32", "LQR_F64", "ROLLCL_F32", "ROLLCL_F64", "ROLLCOST_F32", "ROLLCOST_F64",
+                     "MPPI_F32", "MPPI_F64"]
 # floating-base robots: COMMON from rbd_kernels.hip + the two units of rbd_fb_kernels.hip
 FB_TRANSLATION_UNITS = ["COMMON", "FB_F32", "FB_F64"]
 class _PrioritySlots:
@@ -99,7 +100,7 @@ _HIPCC_SLOTS = _PrioritySlots(max(1, (os.cpu_count() or 2)))
 _TU_COST = {"GRAD_F64": 110, "GRADN_F64": 105, "PASS_F32": 140, "PASS_F64": 125, "GRAD_F32": 60, "GRADN_F32": 57, "MINV_F64": 79, "MINV_F32": 74,
             "RNEA_F64": 50, "RNEA_F32": 47, "FD_F32": 45, "FD_F64": 39, "ROLL_F32": 40, "ROLL_F64": 38, "ROLLG_F32": 4, "ROLLG_F64": 4,
             "LQR_F32": 12, "LQR_F64": 12, "ROLLCL_F32": 40, "ROLLCL_F64": 38, "ROLLCOST_F32": 41, "ROLLCOST_F64": 39,
-            "COMMON": 3}
+            "MPPI_F32": 3, "MPPI_F64": 3, "COMMON": 3}
 
 
 def _run(cmd, what, cost: float = 0.0):
@@ -273,9 +274,10 @@ FAMILIES = {           # family -> units (suffix _F32 / _F64 appended)
     "lqr": ["LQR", "GRAD", "FD", "RNEA", "MINV"],      # rbd_rollout_lqr: the Riccati scan + the same three entry points
     "rollcl": ["ROLLCL"],                       # rbd_rollout_closed_loop: rollout's sweeps with the control law in the time loop
     "rollcost": ["ROLLCOST"],                   # rbd_rollout_cost: the same time loop with the cost accumulated in it
+    "mppi": ["MPPI"],                           # rbd_mppi_update: softmin weights and the weighted sum of du (no dynamics)
 }
 _FAST_UNITS = {"GRAD", "GRADN", "RNEA"}
-_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE", "SO", "FDSO", "ROLL", "ROLLG", "LQR", "ROLLCL", "ROLLCOST"]
+_ALL_FAMILY_UNITS = ["RNEA", "GRAD", "GRADN", "MINV", "FD", "PASS", "EE", "SO", "FDSO", "ROLL", "ROLLG", "LQR", "ROLLCL", "ROLLCOST", "MPPI"]
 
 
 def family_of(symbol: str, has_qdd: bool = True) -> str:
@@ -306,6 +308,8 @@ def family_of(symbol: str, has_qdd: bool = True) -> str:
         return "rollcl"
     if symbol == "rbd_rollout_cost":
         return "rollcost"
+    if symbol in ("rbd_mppi_update", "rbd_mppi_update_workspace_bytes"):
+        return "mppi"
     return "pass"
 
 

@@ -763,6 +763,77 @@ int rollout_cost_launch(const T* q0, const T* qd0, const T* u, const T* k, const
 }
 #endif  // RBD_NEED_ROLLCOST
 
+// rbd_mppi_update's workspace: e [S, P] | eta [P] | the chunk partials [ceil(S / C), T, P, N] when there is more than one chunk
+#if defined(RBD_TU_COMMON) || defined(RBD_NEED_MPPI)
+// S P and T S P n elements whose byte offsets stay far inside int64 (sizes are positive)
+inline bool mppi_sizes_ok(int64_t S, int64_t P, int64_t steps) {
+  const int64_t lim = INT64_MAX / 64;
+  return S <= lim / P && steps <= lim / (S * P) && steps * S * P <= lim / rbdm::N;
+}
+struct MppiWorkspace {
+  int64_t nchunks;
+  size_t off_eta, off_part, total;
+  MppiWorkspace(int64_t S, int64_t P, int64_t steps, size_t esz) {
+    nchunks = (S + RBD_MPPI_CHUNK - 1) / RBD_MPPI_CHUNK;
+    size_t o = align16((size_t)S * (size_t)P * esz);
+    off_eta = o;  o += align16((size_t)P * esz);
+    off_part = o; o += nchunks > 1 ? align16((size_t)nchunks * (size_t)steps * (size_t)P * rbdm::N * esz) : 0;
+    total = o;
+  }
+};
+#endif
+
+#ifdef RBD_NEED_MPPI
+// rbd_mppi_update: weights, the pass over du, the combine (rbd_mppi.h).  Arguments are checked before the first launch.
+template <class T>
+int mppi_launch(const T* J, const T* du, const T* u, const T* lam, const T* u_lo, const T* u_hi, int64_t S, int64_t P,
+                int64_t steps, T* u_out, T* w_out, T* ess_out, int32_t* status_out, void* workspace, size_t wsb, void* stream) {
+  using namespace rbdk;
+  const char* who = "rbd_mppi_update";
+  if (rbdm::FLOATING_BASE) return fail(RBD_ERR_UNSUPPORTED, "%s: fixed-base robots only", who);
+  if (S < 0) return fail(RBD_ERR_ARG, "%s: S < 0", who);
+  if (P < 0) return fail(RBD_ERR_ARG, "%s: P < 0", who);
+  if (steps < 0) return fail(RBD_ERR_ARG, "%s: T < 0", who);
+  if (S == 0 || P == 0 || steps == 0) return 0;
+  if (!J || !du || !u || !lam || !u_out || !status_out)
+    return fail(RBD_ERR_ARG, "%s: J, du, u, lam, u_out and status_out must be non-null", who);
+  if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(RBD_ERR_ARG, "%s: u_lo and u_hi must be both null or both non-null", who);
+  if (!mppi_sizes_ok(S, P, steps)) return fail(RBD_ERR_ARG, "%s: S * P or T * S * P * n too large", who);
+  if (misaligned(u_out, w_out, ess_out, status_out)) return fail(RBD_ERR_ARG, "%s: output buffers must be 16-byte aligned", who);
+  const MppiWorkspace L(S, P, steps, sizeof(T));
+  if (!workspace || wsb < L.total)
+    return fail(RBD_ERR_WORKSPACE, "%s: workspace missing or smaller than rbd_mppi_update_workspace_bytes(S, P, T, .)", who);
+  if (misaligned(workspace)) return fail(RBD_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
+  constexpr int VE = mppi_vec<T>();
+  const int64_t R = P * N;
+  const bool vec = R % VE == 0 && !misaligned(du);
+  const int64_t groups = vec ? R / VE : R;
+  unsigned grid_w, grid_p, grid_c = 0;
+  const bool small = L.nchunks == 1;
+  if (int rc = small ? grid_for(P, MPPI_THREADS, who, &grid_w) : checked_grid(P, who, &grid_w)) return rc;
+  if (int rc = grid_for(steps * L.nchunks * groups, MPPI_THREADS, who, &grid_p)) return rc;
+  if (!small)
+    if (int rc = grid_for(steps * R, MPPI_COMB_O, who, &grid_c)) return rc;
+  char* w = reinterpret_cast<char*>(workspace);
+  T* e_ws = reinterpret_cast<T*>(w);
+  T* eta_ws = reinterpret_cast<T*>(w + L.off_eta);
+  T* part = reinterpret_cast<T*>(w + L.off_part);
+  int rc = small ? launch("rbd_mppi_update (weights) launch", mppi_weights_small_kernel<T>, grid_w, MPPI_THREADS, 0, stream, J, lam,
+                          S, P, e_ws, eta_ws, w_out, ess_out, status_out)
+                 : launch("rbd_mppi_update (weights) launch", mppi_weights_kernel<T>, grid_w, MPPI_W_THREADS, 0, stream, J, lam, S, P,
+                          e_ws, eta_ws, w_out, ess_out, status_out);
+  if (rc != 0) return rc;
+  T* out = small ? u_out : part;
+  rc = vec ? launch("rbd_mppi_update (partials) launch", mppi_partials_kernel<T, VE>, grid_p, MPPI_THREADS, 0, stream, du, u, e_ws,
+                    eta_ws, u_lo, u_hi, S, P, steps, L.nchunks, groups, out)
+           : launch("rbd_mppi_update (partials) launch", mppi_partials_kernel<T, 1>, grid_p, MPPI_THREADS, 0, stream, du, u, e_ws,
+                    eta_ws, u_lo, u_hi, S, P, steps, L.nchunks, groups, out);
+  if (rc != 0 || small) return rc;
+  return launch("rbd_mppi_update (combine) launch", mppi_combine_kernel<T>, grid_c, MPPI_THREADS, 0, stream, part, u, eta_ws, u_lo,
+                u_hi, P, steps * R, L.nchunks, u_out);
+}
+#endif  // RBD_NEED_MPPI
+
 // rbd_rollout_grad's workspace for chunks of Tc steps, R = Tc B flat rows: minv's scratch | qdd [R, N] | dc_du [R, N, 2N] |
 // Minv [R, N, N] | lam [B, 2N]
 #if defined(RBD_TU_COMMON) || defined(RBD_NEED_ROLLG)
@@ -1289,7 +1360,17 @@ RBD_DECLS_SELECTION(f64)
                              const T*, const T*, const T*, const T*, const T*, const T*, const T*, int, const T*, const T*, T,   \
                              T, int, int64_t, int64_t, int64_t, T*, T*, T*, int, T*, void*) RBD_STUB_BODY("rbd_rollout_cost")
 
-#define RBD_DEFS_ROLLG(SFX, T)                                                                                                \
+#define RBD_DEFS_MPPI(SFX, T)                                                                                                    \
+  int rbd_mppi_update_##SFX(const T* J, const T* du, const T* u, const T* lam, const T* u_lo, const T* u_hi, int64_t S,          \
+                            int64_t P, int64_t steps, T* u_out, T* w_out, T* ess_out, int32_t* status_out, void* ws,             \
+                            size_t ws_bytes, void* stream) {                                                                     \
+    RBD_ENTER mppi_launch<T>(J, du, u, lam, u_lo, u_hi, S, P, steps, u_out, w_out, ess_out, status_out, ws, ws_bytes, stream);   \
+  }
+#define RBD_STUBS_MPPI(SFX, T)                                                                                                   \
+  int rbd_mppi_update_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, int64_t, int64_t, int64_t, T*, T*, T*,   \
+                            int32_t*, void*, size_t, void*) RBD_STUB_BODY("rbd_mppi_update")
+
+#define RBD_DEFS_ROLLG(SFX, T)                                                                                           \
   int rbd_rollout_adjoint_##SFX(const T* dc_du, const T* Minv, const T* gq, const T* gqd, int g_final_only, T dt, int integrator, \
                                 int64_t B, int64_t steps, T* lam, T* grad_u, void* stream) {                                     \
     RBD_ENTER rollout_adjoint_launch<T>(dc_du, Minv, gq, gqd, g_final_only, dt, integrator, B, steps, lam, grad_u, stream);      \
@@ -1450,6 +1531,17 @@ RBD_DEFS_ROLLCOST(f64, double)
 RBD_STUBS_ROLLCOST(f64, double)
 #endif
 
+#if defined(RBD_TU_MPPI_F32)
+RBD_DEFS_MPPI(f32, float)
+#elif defined(RBD_STUB_MPPI_F32)
+RBD_STUBS_MPPI(f32, float)
+#endif
+#if defined(RBD_TU_MPPI_F64)
+RBD_DEFS_MPPI(f64, double)
+#elif defined(RBD_STUB_MPPI_F64)
+RBD_STUBS_MPPI(f64, double)
+#endif
+
 #if defined(RBD_TU_ROLLG_F32)
 RBD_DEFS_ROLLG(f32, float)
 #elif defined(RBD_STUB_ROLLG_F32)
@@ -1555,6 +1647,10 @@ size_t rbd_rollout_lqr_workspace_bytes(int64_t B, int64_t Tc, int elem_size) {
   if (elem_size == 4) return LqrWorkspace<float>(B, Tc).total;
   if (elem_size == 8) return LqrWorkspace<double>(B, Tc).total;
   return 0;
+}
+size_t rbd_mppi_update_workspace_bytes(int64_t S, int64_t P, int64_t T, int elem_size) {
+  if (S <= 0 || P <= 0 || T <= 0 || rbdm::FLOATING_BASE || (elem_size != 4 && elem_size != 8) || !mppi_sizes_ok(S, P, T)) return 0;
+  return MppiWorkspace(S, P, T, (size_t)elem_size).total;
 }
 #endif  // RBD_TU_COMMON
 }  // extern "C"

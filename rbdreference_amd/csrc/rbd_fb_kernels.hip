@@ -374,6 +374,10 @@ RBD_DECLS_SELECTION(f64)
                              const T*, T, T, int, int64_t, int64_t, int64_t, T*, T*, T*, int, T*, void*) {                  \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_cost: fixed-base robots only (rbd_rollout has no floating base)");       \
   }                                                                                                                         \
+  int rbd_mppi_update_##SFX(const T*, const T*, const T*, const T*, const T*, const T*, int64_t, int64_t, int64_t, T*, T*, \
+                            T*, int32_t*, void*, size_t, void*) {                                                           \
+    return fail(RBD_ERR_UNSUPPORTED, "rbd_mppi_update: fixed-base robots only (rbd_rollout has no floating base)");        \
+  }                                                                                                                         \
   int rbd_rollout_adjoint_##SFX(const T*, const T*, const T*, const T*, int, T, int, int64_t, int64_t, T*, T*, void*) {    \
     return fail(RBD_ERR_UNSUPPORTED, "rbd_rollout_adjoint: fixed-base robots only (rbd_rollout has no floating base)");    \
   }                                                                                                                         \

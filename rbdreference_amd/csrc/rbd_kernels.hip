@@ -26,7 +26,7 @@
 //   crba, rnea_fpass / rnea_bpass, forward_dynamics(_grad): further rows, same building blocks.
 // The library is built from several translation units of this one file (rbdreference_amd/build.py
 // compiles them in parallel): -DRBD_TU_COMMON, _RNEA_F32, _RNEA_F64, _GRAD_F32, _GRAD_F64,
-// _ROLL_F32, _ROLL_F64 (rbd_rollout.h), _ROLLG_F32, _ROLLG_F64 (rbd_rollout_adj.h), _LQR_F32, _LQR_F64 (rbd_rollout_lqr.h), _ROLLCL_F32, _ROLLCL_F64 (rbd_rollout_cl.h), _ROLLCOST_F32, _ROLLCOST_F64 (rbd_rollout_cost.h), _GRADN_F32, _GRADN_F64 (the qdd = None instantiations of the gradient kernels: half of a gradient unit's compile
+// _ROLL_F32, _ROLL_F64 (rbd_rollout.h), _ROLLG_F32, _ROLLG_F64 (rbd_rollout_adj.h), _LQR_F32, _LQR_F64 (rbd_rollout_lqr.h), _ROLLCL_F32, _ROLLCL_F64 (rbd_rollout_cl.h), _ROLLCOST_F32, _ROLLCOST_F64 (rbd_rollout_cost.h), _MPPI_F32, _MPPI_F64 (rbd_mppi.h), _GRADN_F32, _GRADN_F64 (the qdd = None instantiations of the gradient kernels: half of a gradient unit's compile
 // time), _MINV_F32, _MINV_F64, _FD_F32, _FD_F64, _PASS_F32, _PASS_F64 (each together with -DRBD_TU_SPLIT);
 // without RBD_TU_SPLIT everything is compiled in one unit.
 // -DRBD_FAST_STAGE=1 (first-use family libraries of the gradient, rbdreference_amd/build.py): only the kernel AUTO
@@ -65,6 +65,8 @@
 #define RBD_TU_ROLLCL_F64 1
 #define RBD_TU_ROLLCOST_F32 1
 #define RBD_TU_ROLLCOST_F64 1
+#define RBD_TU_MPPI_F32 1
+#define RBD_TU_MPPI_F64 1
 #endif
 
 // Which kernel families this unit needs (everything it does not need is dropped by the preprocessor,
@@ -108,6 +110,9 @@
 #endif
 #if defined(RBD_TU_ROLLCOST_F32) || defined(RBD_TU_ROLLCOST_F64)
 #define RBD_NEED_ROLLCOST 1
+#endif
+#if defined(RBD_TU_MPPI_F32) || defined(RBD_TU_MPPI_F64)
+#define RBD_NEED_MPPI 1
 #endif
 #include "rbd_spatial.h"
 
@@ -2121,6 +2126,9 @@ __global__ __launch_bounds__(64 * MINV_COLS_W, MINV_COLS_MIN_WAVES) void minv_co
 #endif
 #ifdef RBD_NEED_ROLLCOST
 #include "rbd_rollout_cost.h"
+#endif
+#ifdef RBD_NEED_MPPI
+#include "rbd_mppi.h"
 #endif
 namespace rbdk {
 #ifdef RBD_NO_MINV_LANE
