@@ -3,6 +3,10 @@
     from oracle import c_oracle
     co = c_oracle.COracle(robot)            # builds oracle/_build/librbd_oracle.so with gcc if needed
     c, dc_du = co.rnea_grad(q, qd, qdd)     # [B, n] float64 in -> numpy out, OpenMP over rows
+
+    cf = c_oracle.COracle(robot, real="float")   # the same recursion in plain IEEE float32 (librbd_oracle_f32.so);
+                                                 # inputs and model arrays are cast to float32, outputs are float32
+    co = c_oracle.COracle(model)                 # an oracle.rbd_oracle.OracleModel instead of a robot (perturbed models)
 """
 import ctypes
 import os
@@ -14,17 +18,24 @@ from . import rbd_oracle as orc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "_build", "librbd_oracle.so")
+LIB_F32 = os.path.join(HERE, "_build", "librbd_oracle_f32.so")
+_REALS = {"double": (LIB, [], np.float64, ctypes.c_double),
+          # plain IEEE float32: no FMA contraction, no fast-math; nothing cleverer than the recursion as written
+          "float": (LIB_F32, ["-DRBDO_REAL=float", "-ffp-contract=off"], np.float32, ctypes.c_float)}
 
 
-def build(force: bool = False) -> str:
+def build(force: bool = False, real: str = "double") -> str:
+    lib, flags = _REALS[real][:2]
     src = os.path.join(HERE, "rbd_oracle.c")
-    if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        cmd = ["gcc", "-O2", "-fPIC", "-fopenmp", "-std=c11", "-shared", "-o", LIB, src, "-lm"]
+    if force or not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
+        os.makedirs(os.path.dirname(lib), exist_ok=True)
+        tmp = f"{lib}.{os.getpid()}.tmp"          # (tests in several processes may build at once: rename is atomic)
+        cmd = ["gcc", "-O2", "-fPIC", "-fopenmp", "-std=c11", *flags, "-shared", "-o", tmp, src, "-lm"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("gcc failed for oracle/rbd_oracle.c:\n" + r.stderr)
-    return LIB
+        os.replace(tmp, lib)
+    return lib
 
 
 class _Model(ctypes.Structure):
@@ -34,22 +45,25 @@ class _Model(ctypes.Structure):
 
 
 class COracle:
-    def __init__(self, robot):
-        self.lib = ctypes.CDLL(build())
-        m = orc.model_from_robot(robot)
+    def __init__(self, robot, real: str = "double"):
+        _, _, self.dtype, creal = _REALS[real]
+        self.real = real
+        self.lib = ctypes.CDLL(build(real=real))
+        m = robot if isinstance(robot, orc.OracleModel) else orc.model_from_robot(robot)
         self.n = m.n
+        dt = self.dtype
         self._keep = dict(parent=np.ascontiguousarray(m.parent, dtype=np.int32),
                           prismatic=np.ascontiguousarray(m.prismatic, dtype=np.int32),
-                          S=np.ascontiguousarray(m.S), I=np.ascontiguousarray(m.I),
-                          X0=np.ascontiguousarray(m.X0), Xs=np.ascontiguousarray(m.Xs),
-                          Xc=np.ascontiguousarray(m.Xc), damping=np.ascontiguousarray(m.damping))
+                          S=np.ascontiguousarray(m.S, dtype=dt), I=np.ascontiguousarray(m.I, dtype=dt),
+                          X0=np.ascontiguousarray(m.X0, dtype=dt), Xs=np.ascontiguousarray(m.Xs, dtype=dt),
+                          Xc=np.ascontiguousarray(m.Xc, dtype=dt), damping=np.ascontiguousarray(m.damping, dtype=dt))
         self.model = _Model(m.n, *[self._keep[k].ctypes.data for k in
                                    ("parent", "prismatic", "S", "I", "X0", "Xs", "Xc", "damping")])
         self.lib.rbdo_num_threads.restype = ctypes.c_int
         dp = ctypes.c_void_p
-        self.lib.rbdo_rnea_grad.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, ctypes.c_double, ctypes.c_int,
+        self.lib.rbdo_rnea_grad.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int,
                                             ctypes.c_int64, dp, dp, ctypes.c_int]
-        self.lib.rbdo_rnea.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, ctypes.c_double, ctypes.c_int64,
+        self.lib.rbdo_rnea.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int64,
                                        dp, dp, dp, dp, ctypes.c_int]
         self.lib.rbdo_minv.argtypes = [ctypes.POINTER(_Model), dp, ctypes.c_int, ctypes.c_int64, dp, ctypes.c_int]
 
@@ -57,19 +71,19 @@ class COracle:
     def max_threads(self) -> int:
         return int(self.lib.rbdo_num_threads())
 
-    @staticmethod
-    def _a(x):
-        return np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float64)))
+    def _a(self, x):
+        return np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=self.dtype)))
 
     def rnea_grad(self, q, qd, qdd=None, GRAVITY=-9.81, USE_VELOCITY_DAMPING=False, threads=0, out=None):
         q, qd = self._a(q), self._a(qd)
         qdd = None if qdd is None else self._a(qdd)
         B, n = q.shape
         if out is None:
-            c = np.empty((B, n)); dc = np.empty((B, n, 2 * n))
+            c = np.empty((B, n), dtype=self.dtype); dc = np.empty((B, n, 2 * n), dtype=self.dtype)
         else:                       # reuse caller's buffers (timing loops: no page faults per call)
             c, dc = out
             assert c.shape == (B, n) and dc.shape == (B, n, 2 * n) and c.flags.c_contiguous and dc.flags.c_contiguous
+            assert c.dtype == self.dtype and dc.dtype == self.dtype
         self.lib.rbdo_rnea_grad(ctypes.byref(self.model), q.ctypes.data, qd.ctypes.data,
                                 None if qdd is None else qdd.ctypes.data, float(GRAVITY),
                                 int(USE_VELOCITY_DAMPING), B, c.ctypes.data, dc.ctypes.data, int(threads))
@@ -79,7 +93,8 @@ class COracle:
         q, qd = self._a(q), self._a(qd)
         qdd = None if qdd is None else self._a(qdd)
         B, n = q.shape
-        c = np.empty((B, n)); v = np.empty((B, 6, n)); a = np.empty((B, 6, n)); f = np.empty((B, 6, n))
+        c = np.empty((B, n), dtype=self.dtype)
+        v, a, f = (np.empty((B, 6, n), dtype=self.dtype) for _ in range(3))
         self.lib.rbdo_rnea(ctypes.byref(self.model), q.ctypes.data, qd.ctypes.data,
                            None if qdd is None else qdd.ctypes.data, float(GRAVITY), B,
                            c.ctypes.data, v.ctypes.data, a.ctypes.data, f.ctypes.data, int(threads))
@@ -88,7 +103,7 @@ class COracle:
     def minv(self, q, output_dense=True, threads=0):
         q = self._a(q)
         B, n = q.shape
-        M = np.empty((B, n, n))
+        M = np.empty((B, n, n), dtype=self.dtype)
         self.lib.rbdo_minv(ctypes.byref(self.model), q.ctypes.data, int(bool(output_dense)), B, M.ctypes.data,
                            int(threads))
         return M

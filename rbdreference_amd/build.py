@@ -95,7 +95,15 @@ class _PrioritySlots:
             self.cv.notify_all()
 
 
-_HIPCC_SLOTS = _PrioritySlots(max(1, (os.cpu_count() or 2)))
+def _hipcc_jobs() -> int:
+    """hipcc processes at once: the CPUs THIS process may use (os.cpu_count() is the whole machine's, many times as many on a
+    shared box), and no more than MAX_JOBS where the environment sets one."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2)
+    cap = os.environ.get("MAX_JOBS", "")
+    return max(1, min(n, int(cap)) if cap.isdigit() and int(cap) > 0 else n)
+
+
+_HIPCC_SLOTS = _PrioritySlots(_hipcc_jobs())
 # relative compile cost of the translation units (measured, 30-body robot), scaled by n^2 per robot
 _TU_COST = {"GRAD_F64": 110, "GRADN_F64": 105, "PASS_F32": 140, "PASS_F64": 125, "GRAD_F32": 60, "GRADN_F32": 57, "MINV_F64": 79, "MINV_F32": 74,
             "RNEA_F64": 50, "RNEA_F32": 47, "FD_F32": 45, "FD_F64": 39, "ROLL_F32": 40, "ROLL_F64": 38, "ROLLG_F32": 4, "ROLLG_F64": 4,

@@ -1,0 +1,257 @@
+"""Entry-wise accuracy of every fp32 kernel family of rnea / rnea_grad / minv (run with ``-m gpu`` on a real MI355X).
+
+The yardstick is tests/entrywise.py: per entry, what one float32 rounding of the data does to it (measured with the double
+C oracle) plus 2^-24 of its block; a kernel passes when its worst entry is within ``MARGIN = 4`` (two bits) of what the
+plain-float32 build of the same C oracle loses on the same rows -- ``ratio <= 4 R_ref``, R_ref computed here for every robot,
+regime, variant and tensor.  130 rows (two 64-lane tiles and a ragged one), two regimes (``std``; ``fast0g``: ten times the
+joint velocities and no gravity, so the velocity products set the scale), the nine fixed-base fixture robots, every kernel
+family ``rbd_set_option`` can select (an option for which the library names a kernel that an earlier option already named is
+skipped), and the model-handle library on two robots.  Prebuilt libraries only.  Every case prints
+``kernel  ratio  R_ref  ratio / R_ref``; the measured table is in DESIGN.md §2.1, "Entry-wise fp32 accuracy of the kernel
+families", with the open defects this file marks ``xfail(strict=True)``.
+
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import entrywise as ew
+from conftest import all_golden_names, make_robot
+from test_gpu_parity import _torch, rbd_for
+
+pytestmark = pytest.mark.gpu
+
+# Margin over R_ref per kernel family (the name up to '<'); a family not listed gets ew.MARGIN = 4.
+# The three world-frame IDSVA kernels (rbd_idsva.h, rbd_idsva_pipe.h, rbd_idsva_tree.h, g_rnea_grad_world_kernel) form every
+# entry from composites taken about the WORLD origin: IC = (m, h = m c, Ibar about the origin), BC, f.  A distal joint's row
+# is then the difference of terms the size of m |c|^2 (parallel-axis part of Ibar) and c x F (moment of the subtree's force
+# about the origin), while the entry itself has the size of the link's own inertia and of the torque about its own axis:
+# dc_dqd[i, i] = S_i.BC^T S_i + 2 S_i.IC psid_i is exactly zero and comes out at 1e-7 .. 1e-6.  The column recursions carry
+# every body's quantities in the body's own frame and do not have this term.  The loss is the algorithm's, so these families
+# get the largest margin a family may have; measured worst ratio / R_ref on the robots that stay within it: 9.3 (pipe,
+# random_chain_n7), 12.9 (tree, random_chain_n7).  The robots beyond it are the open defects of XFAIL.
+WORLD_FRAME_MARGIN = 16.0
+# minv_lane_kernel: measured 27.38 = 4.11 R_ref (R_ref 6.66) on random_prismatic_n6, <= 1.07 R_ref on the five other robots.
+# All of it is configuration 27, where the prismatic joint 2 stands at 3.0: joint 1 sees D_1 = 22.3 (parallel axis), and the
+# rank-one downdate Ia_1 = IA_1 - U_1 U_1^T / D_1 (rbd_minv_lane.h: col = fma(-U, U * Dinv, IA)) cancels entries of that size
+# down to D_0 = 0.91.  What is left of the roundings of IA_1 is ONE amplitude on a rank-one pattern (columns 0, 1, 4), and
+# it belongs to the order of the sums, not to the algorithm: the C oracle's own text gives -6.66 Y there in plain float32
+# (that is R_ref), -0.2 Y with FMA contraction and +31.2 Y = 4.7 R_ref with its sums reassociated (gcc -ffast-math); the
+# kernel's factorised sums give +27.4 Y, g_minv_kernel +2.2 Y.  Two bits do not cover the reference recursion's own other
+# summation order in that row, so this family gets three.
+MINV_LANE_MARGIN = 8.0
+FAMILY_MARGIN = {"rnea_grad_idsva_pipe_kernel": WORLD_FRAME_MARGIN, "rnea_grad_tree_kernel": WORLD_FRAME_MARGIN,
+                 "g_rnea_grad_world_kernel": WORLD_FRAME_MARGIN, "minv_lane_kernel": MINV_LANE_MARGIN}
+
+OPTIONS = {"rnea": ("AUTO", "BATCH", "GROUPS"),
+           "rnea_grad": ("AUTO", "TREE", "COLS", "BATCH", "AUTO@2^20"),     # (the last: RBD_OPT_SELECT_BATCH = 2^20, AUTO's large-batch kernel)
+           "minv": ("AUTO", "LANE", "IA8", "FUSED")}
+
+# Open defects: (robot, option that first names the family) -> (family, measured worst ratio / R_ref over both regimes, every
+# variant and tensor).  Beyond 16 R_ref for the reason given at WORLD_FRAME_MARGIN; strict, so a kernel that gets better has to
+# take its line out.  The test checks that the option still names that family.
+XFAIL = {
+    ("atlas_like", "AUTO"): ("rnea_grad_tree_kernel", 413.5),
+    ("iiwa_like", "TREE"): ("rnea_grad_tree_kernel", 530.9),
+    ("iiwa_like", "BATCH"): ("rnea_grad_idsva_pipe_kernel", 404.3),
+    ("quadruped_like", "TREE"): ("rnea_grad_tree_kernel", 27.6),
+    ("random_forest_n8", "TREE"): ("rnea_grad_tree_kernel", 34.9),
+    ("random_limbs_n14", "AUTO"): ("rnea_grad_tree_kernel", 22.9),
+    ("random_tree_n9", "TREE"): ("rnea_grad_tree_kernel", 1534.7),
+    ("random_twochains_n18", "AUTO"): ("rnea_grad_tree_kernel", 39.8),
+}
+XFAIL_GENERIC = {"iiwa_like": ("g_rnea_grad_world_kernel", 351.4), "random_limbs_n14": ("g_rnea_grad_world_kernel", 20.1)}
+
+
+def _margin(kernel):
+    return FAMILY_MARGIN.get(kernel.split("<")[0], ew.MARGIN)
+
+
+def _dev(*arrs):
+    torch = _torch()
+    return [None if a is None else torch.tensor(a, device="cuda:0") for a in arrs]
+
+
+def _np(x):
+    return x.double().cpu().numpy()
+
+
+class _Records(list):
+    """(kernel, variant, tensor, ratio, R_ref, worst entries if beyond the margin) of one robot and kernel."""
+
+    def add(self, robot, regime, kernel, variant, tensor, got, y):
+        r = ew.ratio(_np(got), y.ref, y.Y)
+        rel = r / y.R_ref if y.R_ref > 0 else (0.0 if r == 0 else float("inf"))
+        print(f"ENTRYWISE {robot:20s} {regime:7s} {kernel:48s} {variant:18s} {tensor:6s} ratio {r:9.3f}  R_ref {y.R_ref:7.3f}  ratio/R_ref {rel:7.3f}")
+        bad = None if r <= _margin(kernel) * y.R_ref else ew.worst_entries(_np(got), y.ref, y.Y)
+        self.append((kernel, f"{regime} {variant}", tensor, r, y.R_ref, bad))
+
+    def failures(self):
+        return [(k, v, t, f"ratio {r:.3f} > {_margin(k):g} * R_ref {rr:.3f}", bad) for k, v, t, r, rr, bad in self if bad is not None]
+
+
+def _check_rnea(rec, rbd, name, regime, kernel):
+    g = ew.REGIMES[regime]["GRAVITY"]
+    q, qd, qdd = _dev(*ew.inputs(rbd.n, regime))
+    Y = ew.yardstick(name, regime, "rnea")
+    for t, x in zip("cvaf", rbd.rnea(q, qd, qdd, GRAVITY=g)):
+        rec.add(name, regime, kernel, "rnea", t, x, Y[t])
+    Y0 = ew.yardstick(name, regime, "rnea", has_qdd=False)
+    for t, x in zip("cvaf", rbd.rnea(q, qd, GRAVITY=g)):
+        rec.add(name, regime, kernel, "rnea qdd=None", t, x, Y0[t])
+    c, v, a, f = rbd.rnea(q, qd, qdd, GRAVITY=g, outputs="c")
+    assert v is None and a is None and f is None
+    rec.add(name, regime, kernel, "rnea outputs=c", "c", c, Y["c"])
+
+
+def _check_grad(rec, rbd, name, regime, kernel):
+    g = ew.REGIMES[regime]["GRAVITY"]
+    q, qd, qdd = _dev(*ew.inputs(rbd.n, regime))
+    Y = ew.yardstick(name, regime, "rnea_grad")
+    c, dc = rbd.rnea_grad(q, qd, qdd, GRAVITY=g, return_c=True)
+    rec.add(name, regime, kernel, "rnea_grad", "dc_du", dc, Y["dc_du"]); rec.add(name, regime, kernel, "rnea_grad", "c", c, Y["c"])
+    Yd = ew.yardstick(name, regime, "rnea_grad", damped=True)
+    rec.add(name, regime, kernel, "rnea_grad damped", "dc_du", rbd.rnea_grad(q, qd, qdd, GRAVITY=g, USE_VELOCITY_DAMPING=True), Yd["dc_du"])
+    Y0 = ew.yardstick(name, regime, "rnea_grad", has_qdd=False)
+    c0, dc0 = rbd.rnea_grad(q, qd, GRAVITY=g, return_c=True)
+    rec.add(name, regime, kernel, "rnea_grad qdd=None", "dc_du", dc0, Y0["dc_du"]); rec.add(name, regime, kernel, "rnea_grad qdd=None", "c", c0, Y0["c"])
+    Yr = ew.yardstick(name, regime, "rnea")
+    c2, v, a, f, dc2 = rbd.rnea_and_grad(q, qd, qdd, GRAVITY=g)
+    for t, x in zip("cvaf", (c2, v, a, f)):
+        rec.add(name, regime, kernel, "rnea_and_grad", t, x, Yr[t])
+    rec.add(name, regime, kernel, "rnea_and_grad", "dc_du", dc2, Y["dc_du"])
+
+
+def _check_minv(rec, rbd, name, regime, kernel):
+    (q,) = _dev(ew.inputs(rbd.n, regime)[0])
+    rec.add(name, regime, kernel, "minv dense", "Minv", rbd.minv(q), ew.yardstick(name, regime, "minv")["Minv"])
+    rec.add(name, regime, kernel, "minv upper", "Minv", rbd.minv(q, output_dense=False),
+            ew.yardstick(name, regime, "minv", dense=False)["Minv"])     # (np.triu of the reference)
+
+
+_CHECK = {"rnea": _check_rnea, "rnea_grad": _check_grad, "minv": _check_minv}
+
+
+def _settings(entry, option):
+    from rbdreference_amd import _lib as L
+    if entry == "rnea":
+        return [(L.RBD_OPT_RNEA_KERNEL, OPTIONS[entry].index(option))]
+    if entry == "minv":
+        return [(L.RBD_OPT_MINV_PHASE_A, OPTIONS[entry].index(option))]
+    if option == "AUTO@2^20":
+        return [(L.RBD_OPT_SELECT_BATCH, 1 << 20), (L.RBD_OPT_GRAD_KERNEL, L.RBD_GRAD_KERNEL_AUTO)]
+    return [(L.RBD_OPT_SELECT_BATCH, 0), (L.RBD_OPT_GRAD_KERNEL, OPTIONS[entry].index(option))]
+
+
+def _kernel(rbd, entry, option):
+    """Set the option (the caller restores it) -> the kernel the library names for 130 rows."""
+    from rbdreference_amd import _lib as L
+    assert (L.RBD_RNEA_KERNEL_GROUPS, L.RBD_GRAD_KERNEL_BATCH, L.RBD_MINV_PHASE_A_FUSED) == (2, 3, 3)      # OPTIONS is in the ABI's order
+    for opt, val in _settings(entry, option):
+        rbd._lib.set_option(opt, val)
+    kernel = rbd._lib.kernel_name({"rnea": L.RBD_OP_RNEA, "rnea_grad": L.RBD_OP_RNEA_GRAD, "minv": L.RBD_OP_MINV}[entry], 4, ew.B)
+    if kernel.startswith("minv_cols_kernel"):      # one name, two phase A kernels in front of it (130 rows: AUTO's is IA8)
+        kernel += " A=lane" if option == "LANE" else " A=ia8"
+    return kernel
+
+
+@functools.lru_cache(maxsize=None)
+def run_option(name, entry, option):
+    """One option of one entry point on one robot (fp32, 130 rows, both regimes) -> (kernel, _Records); records is None when
+    an earlier option of OPTIONS[entry] already names this kernel."""
+    rbd = rbd_for(name)
+    try:
+        earlier = {_kernel(rbd, entry, o) for o in OPTIONS[entry][:OPTIONS[entry].index(option)]}
+        kernel = _kernel(rbd, entry, option)
+        if kernel in earlier:
+            return kernel, None
+        rec = _Records()
+        for regime in sorted(ew.REGIMES):
+            _CHECK[entry](rec, rbd, name, regime, kernel)
+        return kernel, rec
+    finally:
+        for opt, _ in _settings(entry, "AUTO") + _settings("rnea_grad", "AUTO"):
+            rbd._lib.set_option(opt, 0)
+
+
+def _cases():
+    for entry, options in OPTIONS.items():
+        for name in all_golden_names():
+            for option in options:
+                known = XFAIL.get((name, option)) if entry == "rnea_grad" else None
+                marks = [pytest.mark.xfail(strict=True, reason=f"{known[0]}: ratio / R_ref = {known[1]} (open defect, DESIGN.md 2.1)")] if known else []
+                yield pytest.param(entry, name, option, marks=marks, id=f"{entry}-{name}-{option}")
+
+
+@pytest.mark.parametrize("entry,name,option", list(_cases()))
+def test_every_fp32_family_entrywise(entry, name, option):
+    kernel, rec = run_option(name, entry, option)
+    if rec is None:
+        pytest.skip(f"the library names {kernel} for this option, which an earlier option already ran")
+    assert rec and not rec.failures(), rec.failures()
+
+
+def test_open_defects_name_the_kernels_that_run():
+    for (name, option), (family, _) in XFAIL.items():
+        kernel, rec = run_option(name, "rnea_grad", option)
+        assert rec is not None and kernel.startswith(family + "<"), (name, option, kernel)
+
+
+@functools.lru_cache(maxsize=None)
+def run_generic(name, which):
+    """The model-handle library, both ways results leave the kernels: 'world' = rnea_grad on AUTO's world-frame kernel;
+    'columns' = rnea, minv and rnea_grad on the column recursions -> _Records."""
+    from rbdreference_amd import RBDReference
+    from rbdreference_amd._lib import RBD_OP_MINV, RBD_OP_RNEA, RBD_OP_RNEA_GRAD
+    from rbdreference_amd.generic import RBD_G_GRAD_KERNEL_AUTO, RBD_G_GRAD_KERNEL_COLUMNS, load_generic_library
+    rbd = RBDReference(make_robot(name), build=False, generic="only")
+    lib = load_generic_library()
+    rec = _Records()
+    q, qd, _ = _dev(*ew.inputs(rbd.n, "std"))
+    rbd.rnea(q, qd)                              # (a handle exists from here on: kernel_name asks the library)
+    try:
+        assert lib.rbd_g_set_grad_kernel(RBD_G_GRAD_KERNEL_AUTO if which == "world" else RBD_G_GRAD_KERNEL_COLUMNS) == 0
+        for staging, tag in ((1, "direct"), (2, "staged")):
+            assert lib.rbd_g_set_output_staging(staging) == 0
+            for regime in sorted(ew.REGIMES):
+                if which == "columns":
+                    _check_rnea(rec, rbd, name, regime, f"{rbd._lib.kernel_name(RBD_OP_RNEA, 4, ew.B)} {tag}")
+                    _check_minv(rec, rbd, name, regime, f"{rbd._lib.kernel_name(RBD_OP_MINV, 4, ew.B)} {tag}")
+                _check_grad(rec, rbd, name, regime, f"{rbd._lib.kernel_name(RBD_OP_RNEA_GRAD, 4, ew.B)} {tag}")
+                assert rbd._lib.served_by_generic()
+    finally:
+        lib.rbd_g_set_grad_kernel(RBD_G_GRAD_KERNEL_AUTO)
+        lib.rbd_g_set_output_staging(0)
+    return rec
+
+
+@pytest.mark.parametrize("name,which", [
+    pytest.param(name, which, id=f"{name}-{which}", marks=[pytest.mark.xfail(
+        strict=True, reason="{}: ratio / R_ref = {} (open defect, DESIGN.md 2.1)".format(*XFAIL_GENERIC[name]))] if which == "world" else [])
+    for name in ("iiwa_like", "random_limbs_n14") for which in ("columns", "world")])
+def test_model_handle_library_entrywise(name, which):
+    rec = run_generic(name, which)
+    kernels = {k.split("<")[0] for k, *_ in rec}
+    assert kernels == ({"g_rnea_grad_world_kernel"} if which == "world" else {"g_rnea_kernel", "g_minv_kernel", "g_rnea_grad_kernel"}), kernels
+    assert not rec.failures(), rec.failures()
+
+
+def test_every_fp32_kernel_of_the_selection_tables_was_measured():
+    """The kernels this file measures contain every fp32 name tests/test_kernel_selection.py pins, for the robots the two
+    files share (the records are those of the tests above when they ran in this process)."""
+    from test_kernel_selection import GRAD, MINV, RNEA
+
+    def flat(x):
+        return {x} if isinstance(x, str) else set().union(*(flat(y) for y in x))
+    shared = sorted(set(RNEA) & set(all_golden_names()))
+    assert shared == ["iiwa_like", "random_chain_n7", "random_forest_n8", "random_limbs_n14"]
+    for name in shared:
+        want = {s % "float" for s in RNEA[name]} | flat(GRAD[name][4]) | {s % "float" for s in MINV[name]}
+        ran = set()
+        for entry, options in OPTIONS.items():
+            for option in options:
+                kernel, rec = run_option(name, entry, option)
+                if rec:                                   # (measured: records exist, within the margin or not)
+                    ran.add(kernel.split(" ")[0])
+        assert want <= ran, (name, sorted(want - ran))
