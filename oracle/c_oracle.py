@@ -66,6 +66,14 @@ class COracle:
         self.lib.rbdo_rnea.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int64,
                                        dp, dp, dp, dp, ctypes.c_int]
         self.lib.rbdo_minv.argtypes = [ctypes.POINTER(_Model), dp, ctypes.c_int, ctypes.c_int64, dp, ctypes.c_int]
+        self.lib.rbdo_crba.argtypes = [ctypes.POINTER(_Model), dp, ctypes.c_int64, dp, ctypes.c_int]
+        self.lib.rbdo_aba.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int64, dp, ctypes.c_int]
+        self.lib.rbdo_forward_dynamics.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int64, dp, ctypes.c_int]
+        self.lib.rbdo_forward_dynamics_grad.argtypes = [ctypes.POINTER(_Model), dp, dp, dp, creal, ctypes.c_int64, dp, dp,
+                                                        ctypes.c_int]
+        for fn in ("rbdo_rnea_grad", "rbdo_rnea", "rbdo_minv", "rbdo_crba", "rbdo_aba", "rbdo_forward_dynamics",
+                   "rbdo_forward_dynamics_grad"):
+            getattr(self.lib, fn).restype = None
 
     @property
     def max_threads(self) -> int:
@@ -107,3 +115,36 @@ class COracle:
         self.lib.rbdo_minv(ctypes.byref(self.model), q.ctypes.data, int(bool(output_dense)), B, M.ctypes.data,
                            int(threads))
         return M
+
+    def crba(self, q, threads=0):
+        q = self._a(q)
+        B, n = q.shape
+        H = np.empty((B, n, n), dtype=self.dtype)
+        self.lib.rbdo_crba(ctypes.byref(self.model), q.ctypes.data, B, H.ctypes.data, int(threads))
+        return H
+
+    def aba(self, q, qd, tau, GRAVITY=-9.81, threads=0):
+        q, qd, tau = self._a(q), self._a(qd), self._a(tau)
+        B, n = q.shape
+        qdd = np.empty((B, n), dtype=self.dtype)
+        self.lib.rbdo_aba(ctypes.byref(self.model), q.ctypes.data, qd.ctypes.data, tau.ctypes.data, float(GRAVITY), B,
+                          qdd.ctypes.data, int(threads))
+        return qdd
+
+    def forward_dynamics(self, q, qd, u, GRAVITY=-9.81, threads=0):
+        """``minv(q) @ (u - rnea(q, qd).c)`` -> qdd ``[B, n]``."""
+        q, qd, u = self._a(q), self._a(qd), self._a(u)
+        B, n = q.shape
+        qdd = np.empty((B, n), dtype=self.dtype)
+        self.lib.rbdo_forward_dynamics(ctypes.byref(self.model), q.ctypes.data, qd.ctypes.data, u.ctypes.data, float(GRAVITY), B,
+                                       qdd.ctypes.data, int(threads))
+        return qdd
+
+    def forward_dynamics_grad(self, q, qd, u, GRAVITY=-9.81, threads=0):
+        """-> (qdd ``[B, n]``, ``[fd_dq | fd_dqd]`` ``[B, n, 2n]``): ``-minv(q) @ rnea_grad(q, qd, qdd)`` at the composition's qdd."""
+        q, qd, u = self._a(q), self._a(qd), self._a(u)
+        B, n = q.shape
+        qdd = np.empty((B, n), dtype=self.dtype); d = np.empty((B, n, 2 * n), dtype=self.dtype)
+        self.lib.rbdo_forward_dynamics_grad(ctypes.byref(self.model), q.ctypes.data, qd.ctypes.data, u.ctypes.data, float(GRAVITY),
+                                            B, qdd.ctypes.data, d.ctypes.data, int(threads))
+        return qdd, d

@@ -8,6 +8,10 @@
  * every host core), since a numpy port says more about the Python interpreter than about the CPU.
  * Only tests/, __graft_entry__.smoke()/build() and bench.py may build, load or call it.
  *
+ * crba, aba, forward_dynamics and forward_dynamics_grad (RBDReference.py:1091-1124, 940-1024, 1371-1384) restate
+ * oracle/rbd_oracle.py's: aba is its own three sweeps, the two compositions are built from minv_one, rnea_one and
+ * rnea_grad_one with left-to-right sums.
+ *
  * Pinning: tests/test_c_oracle.py holds it to the golden vectors generated from the real reference
  * (tests/golden) at 1e-12 and to the numpy oracle on random inputs.
  *
@@ -303,6 +307,165 @@ static void minv_one(const rbdo_model* m, const real* q, int dense, real* Minv, 
       for (int cc = 0; cc < r; ++cc) Minv[r * n + cc] = Minv[cc * n + r];
 }
 
+/* y = X^T A X (6x6), the two products of minv_one's articulated-inertia step: T = A X, y = X^T T. */
+static void xtax(const real* X, const real* A, real* y) {
+  real T[36];
+  for (int r = 0; r < 6; ++r)
+    for (int cc = 0; cc < 6; ++cc) {
+      real s = 0;
+      for (int k = 0; k < 6; ++k) s += A[r * 6 + k] * X[k * 6 + cc];
+      T[r * 6 + cc] = s;
+    }
+  for (int r = 0; r < 6; ++r)
+    for (int cc = 0; cc < 6; ++cc) {
+      real s = 0;
+      for (int k = 0; k < 6; ++k) s += X[k * 6 + r] * T[k * 6 + cc];
+      y[r * 6 + cc] = s;
+    }
+}
+
+/* crba (RBDReference.py:1091-1124, fixed base), as oracle/rbd_oracle.py crba.  Scratch: IC [n][36], X [n][36]. */
+static void crba_one(const rbdo_model* m, const real* q, real* H, real* scratch) {
+  const int n = m->n;
+  real* IC = scratch;
+  real* X = IC + 36 * n;
+  memcpy(IC, m->I, sizeof(real) * 36 * n);
+  memset(H, 0, sizeof(real) * n * n);
+  for (int i = 0; i < n; ++i) xmat(m, i, q[i], X + i * 36);
+  for (int i = n - 1; i >= 0; --i) {                                         /* :1101 */
+    const int p = m->parent[i];
+    if (p != -1) {
+      real y[36];
+      xtax(X + i * 36, IC + i * 36, y);
+      for (int k = 0; k < 36; ++k) IC[p * 36 + k] += y[k];
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    real fh[6], t[6], s = 0;
+    mv(IC + i * 36, m->S + i * 6, fh);                                       /* :1109 */
+    for (int r = 0; r < 6; ++r) s += m->S[i * 6 + r] * fh[r];
+    H[i * n + i] = s;                                                        /* :1110 */
+    int j = i;
+    while (m->parent[j] > -1) {                                              /* :1113 */
+      mtv(X + j * 36, fh, t);                                                /* :1116 */
+      for (int r = 0; r < 6; ++r) fh[r] = t[r];
+      j = m->parent[j];
+      s = 0;
+      for (int r = 0; r < 6; ++r) s += m->S[j * 6 + r] * fh[r];
+      H[i * n + j] = s;                                                      /* :1121 */
+      H[j * n + i] = s;
+    }
+  }
+}
+
+/* aba (RBDReference.py:940-1024, fixed base, the np.matrix reading of :984), as oracle/rbd_oracle.py aba.
+ * Scratch: X [n][36], IA [n][36], v, c, a, pA, U [n][6] each, d [n], u [n]. */
+static void aba_one(const rbdo_model* m, const real* q, const real* qd, const real* tau, real g, real* qdd, real* scratch) {
+  const int n = m->n;
+  real* X = scratch;
+  real* IA = X + 36 * n;
+  real* v = IA + 36 * n;
+  real* c = v + 6 * n;
+  real* a = c + 6 * n;
+  real* pA = a + 6 * n;
+  real* U = pA + 6 * n;
+  real* d = U + 6 * n;
+  real* u = d + n;
+  real a0[6] = {0, 0, 0, 0, 0, -g};                                          /* :954-955 */
+  memcpy(IA, m->I, sizeof(real) * 36 * n);                                   /* :972 */
+  for (int i = 0; i < n; ++i) {
+    const int p = m->parent[i];
+    const real* S = m->S + i * 6;
+    real* Xi = X + i * 36;
+    real* vi = v + i * 6;
+    xmat(m, i, q[i], Xi);
+    if (p == -1) {
+      for (int r = 0; r < 6; ++r) { vi[r] = S[r] * qd[i]; c[i * 6 + r] = 0; }   /* :963 */
+    } else {
+      real t[6];
+      mv(Xi, v + p * 6, t);
+      for (int r = 0; r < 6; ++r) vi[r] = t[r] + S[r] * qd[i];               /* :966-967 */
+      crm_mul(vi, S, t);
+      for (int r = 0; r < 6; ++r) c[i * 6 + r] = t[r] * qd[i];               /* :968 */
+    }
+    real Iv[6];
+    mv(m->I + i * 36, vi, Iv);
+    fxv(vi, Iv, pA + i * 6);                                                 /* :974-984 */
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    const int p = m->parent[i];
+    const real* S = m->S + i * 6;
+    real* Ui = U + i * 6;
+    mv(IA + i * 36, S, Ui);                                                  /* :990 */
+    real di = 0, ps = 0;
+    for (int r = 0; r < 6; ++r) di += Ui[r] * S[r];
+    d[i] = di;                                                               /* :991 */
+    for (int r = 0; r < 6; ++r) ps += pA[i * 6 + r] * S[r];
+    u[i] = tau[i] - ps;                                                      /* :992 */
+    if (p != -1) {
+      real Ia[36], Iac[6], pa[6], y[36], t[6];
+      for (int r = 0; r < 6; ++r)
+        for (int cc = 0; cc < 6; ++cc) Ia[r * 6 + cc] = IA[i * 36 + r * 6 + cc] - Ui[r] * Ui[cc] / di;   /* :996-997 */
+      mv(Ia, c + i * 6, Iac);
+      const real ud = u[i] / di;
+      for (int r = 0; r < 6; ++r) pa[r] = pA[i * 6 + r] + Iac[r] + Ui[r] * ud;   /* :999 */
+      xtax(X + i * 36, Ia, y);
+      for (int k = 0; k < 36; ++k) IA[p * 36 + k] += y[k];                   /* :1001-1004 */
+      mtv(X + i * 36, pa, t);
+      for (int r = 0; r < 6; ++r) pA[p * 6 + r] += t[r];                     /* :1006-1007 */
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const int p = m->parent[i];
+    real t[6], s = 0;
+    mv(X + i * 36, p == -1 ? a0 : a + p * 6, t);
+    for (int r = 0; r < 6; ++r) a[i * 6 + r] = t[r] + c[i * 6 + r];          /* :1015 / :1017 */
+    for (int r = 0; r < 6; ++r) s += U[i * 6 + r] * a[i * 6 + r];
+    qdd[i] = (u[i] - s) / d[i];                                              /* :1020-1021 */
+    for (int r = 0; r < 6; ++r) a[i * 6 + r] += m->S[i * 6 + r] * qdd[i];    /* :1022 */
+  }
+}
+
+/* forward_dynamics (RBDReference.py:1371-1374): qdd = minv(q) (u - rnea(q, qd).c), the sums left to right.
+ * Minv [n][n] comes back dense.  Scratch (fd_scratch): minv_one's, then c [n], v, a, f [6][n] each, X [n][36]. */
+static size_t minv_scratch(int n) { return (size_t)(36 * n + 6 * n * n + 6 * n + n + 36 * n); }
+static size_t fd_scratch(int n) { return minv_scratch(n) + (size_t)(n + 18 * n + 36 * n); }
+static size_t grad_scratch(int n) { return (size_t)(18 * n + 36 * n + 18 * n * n); }
+static void fd_one(const rbdo_model* m, const real* q, const real* qd, const real* u, real g, real* qdd, real* Minv, real* scratch) {
+  const int n = m->n;
+  real* c = scratch + minv_scratch(n);
+  real* v = c + n;
+  real* a = v + 6 * n;
+  real* f = a + 6 * n;
+  real* X = f + 6 * n;
+  rnea_one(m, q, qd, NULL, g, c, v, a, f, X);                                /* :1372 */
+  minv_one(m, q, 1, Minv, scratch);                                          /* :1373 */
+  for (int i = 0; i < n; ++i) {                                              /* :1374 */
+    real s = 0;
+    for (int j = 0; j < n; ++j) s += Minv[i * n + j] * (u[j] - c[j]);
+    qdd[i] = s;
+  }
+}
+
+/* forward_dynamics_grad (RBDReference.py:1376-1384): [fd_dq | fd_dqd] = -minv(q) rnea_grad(q, qd, qdd) at the composition's qdd,
+ * the sums left to right.  Scratch: fd_one's, then rnea_grad_one's, then Minv [n][n], c [n], dc_du [n][2n]. */
+static void fd_grad_one(const rbdo_model* m, const real* q, const real* qd, const real* u, real g, real* qdd, real* fd_du,
+                        real* scratch) {
+  const int n = m->n;
+  real* gs = scratch + fd_scratch(n);
+  real* Minv = gs + grad_scratch(n);
+  real* c = Minv + n * n;
+  real* dc = c + n;
+  fd_one(m, q, qd, u, g, qdd, Minv, scratch);                                /* :1377 */
+  rnea_grad_one(m, q, qd, qdd, g, 0, c, dc, gs);                             /* :1378 */
+  for (int i = 0; i < n; ++i)                                                /* :1380-1383 */
+    for (int k = 0; k < 2 * n; ++k) {
+      real s = 0;
+      for (int j = 0; j < n; ++j) s += -Minv[i * n + j] * dc[j * 2 * n + k];
+      fd_du[i * 2 * n + k] = s;
+    }
+}
+
 /* ---- batched entry points (ctypes) ------------------------------------------------------------ */
 int rbdo_num_threads(void) {
 #ifdef _OPENMP
@@ -364,6 +527,78 @@ void rbdo_minv(const rbdo_model* m, const real* q, int dense, int64_t B, real* M
 #pragma omp for schedule(static)
 #endif
     for (int64_t b = 0; b < B; ++b) minv_one(m, q + b * n, dense, Minv + b * n * n, scratch);
+    free(scratch);
+  }
+}
+
+void rbdo_crba(const rbdo_model* m, const real* q, int64_t B, real* H, int threads) {
+  const int n = m->n;
+  const size_t ns = (size_t)(72 * n);
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+#pragma omp parallel
+#endif
+  {
+    real* scratch = (real*)malloc(sizeof(real) * ns);
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t b = 0; b < B; ++b) crba_one(m, q + b * n, H + b * n * n, scratch);
+    free(scratch);
+  }
+}
+
+void rbdo_aba(const rbdo_model* m, const real* q, const real* qd, const real* tau, real g, int64_t B, real* qdd, int threads) {
+  const int n = m->n;
+  const size_t ns = (size_t)(72 * n + 30 * n + 2 * n);
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+#pragma omp parallel
+#endif
+  {
+    real* scratch = (real*)malloc(sizeof(real) * ns);
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t b = 0; b < B; ++b) aba_one(m, q + b * n, qd + b * n, tau + b * n, g, qdd + b * n, scratch);
+    free(scratch);
+  }
+}
+
+void rbdo_forward_dynamics(const rbdo_model* m, const real* q, const real* qd, const real* u, real g, int64_t B, real* qdd,
+                           int threads) {
+  const int n = m->n;
+  const size_t ns = fd_scratch(n) + (size_t)(n * n);
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+#pragma omp parallel
+#endif
+  {
+    real* scratch = (real*)malloc(sizeof(real) * ns);
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t b = 0; b < B; ++b)
+      fd_one(m, q + b * n, qd + b * n, u + b * n, g, qdd + b * n, scratch + fd_scratch(n), scratch);
+    free(scratch);
+  }
+}
+
+void rbdo_forward_dynamics_grad(const rbdo_model* m, const real* q, const real* qd, const real* u, real g, int64_t B, real* qdd,
+                                real* fd_du, int threads) {
+  const int n = m->n;
+  const size_t ns = fd_scratch(n) + grad_scratch(n) + (size_t)(n * n + n + 2 * n * n);
+#ifdef _OPENMP
+  if (threads > 0) omp_set_num_threads(threads);
+#pragma omp parallel
+#endif
+  {
+    real* scratch = (real*)malloc(sizeof(real) * ns);
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int64_t b = 0; b < B; ++b)
+      fd_grad_one(m, q + b * n, qd + b * n, u + b * n, g, qdd + b * n, fd_du + b * 2 * n * n, scratch);
     free(scratch);
   }
 }

@@ -79,16 +79,17 @@ def _np(x):
 
 class _Records(list):
     """(kernel, variant, tensor, ratio, R_ref, worst entries if beyond the margin) of one robot and kernel."""
+    margin = staticmethod(_margin)        # kernel label -> margin over R_ref
 
     def add(self, robot, regime, kernel, variant, tensor, got, y):
         r = ew.ratio(_np(got), y.ref, y.Y)
         rel = r / y.R_ref if y.R_ref > 0 else (0.0 if r == 0 else float("inf"))
         print(f"ENTRYWISE {robot:20s} {regime:7s} {kernel:48s} {variant:18s} {tensor:6s} ratio {r:9.3f}  R_ref {y.R_ref:7.3f}  ratio/R_ref {rel:7.3f}")
-        bad = None if r <= _margin(kernel) * y.R_ref else ew.worst_entries(_np(got), y.ref, y.Y)
+        bad = None if r <= self.margin(kernel) * y.R_ref else ew.worst_entries(_np(got), y.ref, y.Y)
         self.append((kernel, f"{regime} {variant}", tensor, r, y.R_ref, bad))
 
     def failures(self):
-        return [(k, v, t, f"ratio {r:.3f} > {_margin(k):g} * R_ref {rr:.3f}", bad) for k, v, t, r, rr, bad in self if bad is not None]
+        return [(k, v, t, f"ratio {r:.3f} > {self.margin(k):g} * R_ref {rr:.3f}", bad) for k, v, t, r, rr, bad in self if bad is not None]
 
 
 def _check_rnea(rec, rbd, name, regime, kernel):
