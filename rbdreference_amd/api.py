@@ -20,7 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import RbdLibrary
+from . import _rollout_args as _ra
+from ._lib import RBD_INTEGRATORS, RbdLibrary
 from .packer import PackedModel, pack_robot
 
 __all__ = ["RBDReference", "BoundLaunch"]
@@ -899,63 +900,26 @@ class RBDReference:
         ``rollout_grad`` on the saved trajectory (once differentiable), so ``loss(q, qd).backward()`` fills ``q0.grad``,
         ``qd0.grad`` and ``u.grad``.  With ``trajectory=False`` the trajectory is still computed and kept for the
         backward pass; the last slice is returned."""
-        from ._lib import RBD_INTEGRATORS
-        if self.model.floating:
-            raise NotImplementedError("rollout: fixed-base robots only (a floating base needs an integrator on SE(3))")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"rollout: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        who, n = "rollout", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator, why="a floating base needs an integrator on SE(3)")
         if differentiable:
             if not all(isinstance(x, torch.Tensor) for x in (q0, qd0, u)):
                 raise TypeError("rollout: differentiable=True takes torch tensors (autograd does not see numpy arrays)")
             return _rollout_function()(q0, qd0, u, self, float(dt), float(GRAVITY), integrator, bool(trajectory))
-        n = self.n
-        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
-        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"rollout: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        unb = len(sq) == 1
-        B = 1 if unb else sq[0]
-        shared = len(su) == 2
-        if unb and not shared:
-            raise ValueError(f"rollout: q0 [{n}] takes u [T, {n}], got {su}")
-        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
-            raise ValueError(f"rollout: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
-        T = su[0]
-        if T == 0:
-            raise ValueError("rollout: u holds no step (T == 0)")
-        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
-        if isinstance(u, torch.Tensor):
-            if is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            if u.device != dev or u.dtype != dtp:
-                raise TypeError("all inputs must share device and dtype")
-        else:
-            if not is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            u = torch.as_tensor(np.asarray(u, dtype=np.float64), device=dev)
-        u = u.contiguous()
+        unb, B, T, shared = _ra.check_shapes(who, n, q0, qd0, u)
+        (q0, qd0), cx = _ra.Ctx.from_prep(self._prep(q0, qd0))
+        u = cx.tensor(u)
+        dev, dtp = cx.dev, cx.dtp
         with torch.cuda.device(dev):
             shape = (T, B, n) if trajectory else (B, n)
             q = torch.empty(shape, device=dev, dtype=dtp)
             qd = torch.empty(shape, device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             self._lib.check(self._fn("rbd_rollout", dtp)(
                 self._ptr(q0), self._ptr(qd0), self._ptr(u), int(shared), float(dt), float(GRAVITY), RBD_INTEGRATORS[integrator],
-                B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), st))
+                B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), cx.stream()))
         if unb:
             q, qd = q.squeeze(-2), qd.squeeze(-2)
-        return (q.cpu().numpy(), qd.cpu().numpy()) if is_np else (q, qd)
-
-    @staticmethod
-    def _check_row_alpha(who, row_alpha, alpha, k, lead):
-        """``row_alpha``: one step size per row, instead of ``alpha`` (which must keep its default) and with ``k``."""
-        if row_alpha is None:
-            return
-        if np.shape(alpha) != () or isinstance(alpha, torch.Tensor) or float(alpha) != 1.0:
-            raise ValueError(f"{who}: give alpha or row_alpha, not both")
-        if k is None:
-            raise ValueError(f"{who}: row_alpha scales k, which is missing")
-        if tuple(np.shape(row_alpha)) != tuple(lead):
-            raise ValueError(f"{who}: row_alpha must be {list(lead)} (one step size per row), got {tuple(np.shape(row_alpha))}")
+        return cx.to_caller((q, qd))
 
     # ---- closed-loop rollouts: rbd_rollout_closed_loop, the control law u = u + alpha k + K dx inside the time loop ----
     def rollout_closed_loop(self, q0, qd0, u, q_ref, qd_ref, K, dt, k=None, alpha=1.0, q0_ref=None, qd0_ref=None,
@@ -982,95 +946,37 @@ class RBDReference:
         step size instead (it needs ``k`` and the default ``alpha``): the forward pass of an optimiser that accepts or
         rejects per row.  numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's
         current stream.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
-        who = "rollout_closed_loop"
-        if self.model.floating:
-            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
-        n = self.n
-        sq = tuple(np.shape(q0))                  # shapes first: refused before anything touches the GPU
-        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"{who}: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        unb = len(sq) == 1
-        lead = () if unb else (sq[0],)
-        B = 1 if unb else sq[0]
-        su = tuple(np.shape(u))
-        if len(su) != len(lead) + 2 or su[1:] != lead + (n,):
-            raise ValueError(f"{who}: u must be {['T', *lead, n]} (time-major), got {su}")
-        T = su[0]
-        if T == 0:
-            raise ValueError(f"{who}: u holds no step (T == 0)")
-        for name, x, want in (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
-                              ("q0_ref", q0_ref, sq), ("qd0_ref", qd0_ref, sq)):
-            if x is None:
-                if name in ("q_ref", "qd_ref", "K"):
-                    raise ValueError(f"{who}: {name} is required")
-                continue
-            if tuple(np.shape(x)) != want:
-                raise ValueError(f"{who}: {name} must be {list(want)}, got {tuple(np.shape(x))}")
+        who, n = "rollout_closed_loop", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
+        unb, B, T, _ = _ra.check_shapes(who, n, q0, qd0, u, shared_u=False)
+        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))
+        _ra.check_named_shapes(who, (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
+                                    ("q0_ref", q0_ref, sq), ("qd0_ref", qd0_ref, sq)), required=("q_ref", "qd_ref", "K"))
         if (q0_ref is None) != (qd0_ref is None):
             raise ValueError(f"{who}: give q0_ref and qd0_ref together, or neither (they default to q0, qd0)")
-        if (u_min is None) != (u_max is None):
-            raise ValueError(f"{who}: give u_min and u_max together, or neither")
-        for name, x in (("u_min", u_min), ("u_max", u_max)):
-            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
-                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
-        sa = tuple(np.shape(alpha))
-        if len(sa) > 1 or (len(sa) == 1 and sa[0] == 0):
-            raise ValueError(f"{who}: alpha must be a float or a non-empty 1-D sequence of step sizes, got shape {sa}")
-        A = sa[0] if sa else None
-        self._check_row_alpha(who, row_alpha, alpha, k, lead)
-        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
-
-        def dev_of(x, dtype=None):
-            if isinstance(x, torch.Tensor):
-                if is_np:
-                    raise TypeError("mixing numpy and torch inputs is not supported")
-                if x.device != dev or x.dtype != dtp:
-                    raise TypeError("all inputs must share device and dtype")
-                return x.contiguous()
-            if not is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
-
-        u, q_ref, qd_ref, K = (dev_of(x) for x in (u, q_ref, qd_ref, K))
-        k = None if k is None else dev_of(k)
-        q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (dev_of(q0_ref), dev_of(qd0_ref))
+        _ra.check_limits(who, u_min, u_max, n)
+        A = _ra.check_alpha(who, alpha)
+        _ra.check_row_alpha(who, row_alpha, alpha, k, sq[:-1])
+        (q0, qd0), cx = _ra.Ctx.from_prep(self._prep(q0, qd0))
+        u, q_ref, qd_ref, K, k = (cx.tensor(x) for x in (u, q_ref, qd_ref, K, k))
+        q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (cx.tensor(q0_ref), cx.tensor(qd0_ref))
+        dev, dtp = cx.dev, cx.dtp
         with torch.cuda.device(dev):
-            lims = [None, None]
-            if u_min is not None:
-                for i, x in enumerate((u_min, u_max)):
-                    x = x.to(device=dev, dtype=dtp) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
-                    lims[i] = x.expand(n).contiguous()
-            rows = B * (A or 1)
-            if A is not None:
-                q0, qd0 = q0.repeat(A, 1), qd0.repeat(A, 1)          # row a B + b starts where row b does
-            al = None
-            if row_alpha is not None:
-                al = dev_of(row_alpha).reshape(rows)
-            elif k is not None:
-                if A is None:
-                    al = torch.full((rows,), float(alpha), device=dev, dtype=dtp)
-                else:
-                    a1 = alpha.to(device=dev, dtype=dtp) if isinstance(alpha, torch.Tensor) else torch.as_tensor(np.asarray(alpha, dtype=np.float64), device=dev).to(dtp)
-                    al = a1.repeat_interleave(B).contiguous()
+            lo, hi = cx.limits(u_min, u_max, n)
+            q0, qd0, al, rows = cx.alpha_rows(q0, qd0, alpha, A, row_alpha, k, B)
             q = torch.empty((T, rows, n) if trajectory else (rows, n), device=dev, dtype=dtp)
             qd = torch.empty_like(q)
             ua = torch.empty((T, rows, n), device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             self._lib.check(self._fn("rbd_rollout_closed_loop", dtp)(
                 self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(k), self._ptr(K), self._ptr(q0_ref), self._ptr(qd0_ref),
-                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(lims[0]), self._ptr(lims[1]), float(dt), float(GRAVITY),
-                RBD_INTEGRATORS[integrator], rows, B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), self._ptr(ua), st))
+                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(lo), self._ptr(hi), float(dt), float(GRAVITY),
+                RBD_INTEGRATORS[integrator], rows, B, T, self._ptr(q), self._ptr(qd), int(bool(trajectory)), self._ptr(ua), cx.stream()))
         outs = []
         for x in (q, qd, ua):
             if A is not None:
                 x = x.view(*x.shape[:-2], A, B, n)
-            if unb:
-                x = x.squeeze(-2)
-            outs.append(x.cpu().numpy() if is_np else x)
-        return tuple(outs)
+            outs.append(x.squeeze(-2) if unb else x)
+        return cx.to_caller(tuple(outs))
 
     # ---- rollouts that return their cost: rbd_rollout_cost, the quadratic cost accumulated inside the time loop ----------
     def rollout_cost(self, q0, qd0, u, dt, cost, K=None, q_ref=None, qd_ref=None, k=None, alpha=1.0, du=None, q0_ref=None,
@@ -1101,28 +1007,16 @@ class RBDReference:
 
         Robots with PRISMATIC joints: nothing here differentiates, but gains that come from ``rollout_lqr`` inherit its
         caveat (``rnea_grad``'s ``dc_dq`` is not the q-derivative for such joints).  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
         from .cost import QuadraticCost
-        who = "rollout_cost"
-        if self.model.floating:
-            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        who, n = "rollout_cost", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
         if not isinstance(cost, QuadraticCost):
             raise TypeError(f"{who}: cost must be a QuadraticCost")
         if return_final and return_trajectory:
             raise ValueError(f"{who}: give return_final or return_trajectory, not both (the final state is the trajectory's last slice)")
-        n = self.n
-        sq = tuple(np.shape(q0))                  # shapes first: refused before anything touches the GPU
-        if len(sq) != 2 or sq[1] != n or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"{who}: q0 and qd0 must both be [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        B = sq[0]
+        _, B, T, _ = _ra.check_shapes(who, n, q0, qd0, u, unbatched=False, b_nom=True)
         su = tuple(np.shape(u))
-        if len(su) != 3 or su[2] != n or su[1] == 0 or B % su[1] != 0:
-            raise ValueError(f"{who}: u must be [T, B_nom, {n}] (time-major) with B_nom dividing B = {B}, got {su}")
-        T, Bn = su[0], su[1]
-        if T == 0:
-            raise ValueError(f"{who}: u holds no step (T == 0)")
+        Bn = su[1]
         if K is None:
             if any(x is not None for x in (q_ref, qd_ref, q0_ref, qd0_ref)):
                 raise ValueError(f"{who}: q_ref, qd_ref, q0_ref and qd0_ref belong to the feedback term; K is missing")
@@ -1133,62 +1027,25 @@ class RBDReference:
                 raise ValueError(f"{who}: give q0_ref and qd0_ref together, or neither (they default to q0, qd0)")
             if q0_ref is None and Bn != B:
                 raise ValueError(f"{who}: a nominal of {Bn} rows against {B} rows needs q0_ref and qd0_ref [{Bn}, {n}]")
-        sa = tuple(np.shape(alpha))
-        if len(sa) > 1 or (len(sa) == 1 and sa[0] == 0):
-            raise ValueError(f"{who}: alpha must be a float or a non-empty 1-D sequence of step sizes, got shape {sa}")
-        A = sa[0] if sa else None
-        self._check_row_alpha(who, row_alpha, alpha, k, (B,))
+        A = _ra.check_alpha(who, alpha)
+        _ra.check_row_alpha(who, row_alpha, alpha, k, (B,))
         if A is not None and Bn != B:
             raise ValueError(f"{who}: a 1-D alpha shares one nominal of B rows among its candidates; u has {Bn} rows, q0 {B}")
         lead_du = (T,) + (() if A is None else (A,)) + (B, n)
-        for name, x, want in (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
-                              ("q0_ref", q0_ref, (Bn, n)), ("qd0_ref", qd0_ref, (Bn, n)), ("du", du, lead_du)):
-            if x is not None and tuple(np.shape(x)) != want:
-                raise ValueError(f"{who}: {name} must be {list(want)}, got {tuple(np.shape(x))}")
-        if (u_min is None) != (u_max is None):
-            raise ValueError(f"{who}: give u_min and u_max together, or neither")
-        for name, x in (("u_min", u_min), ("u_max", u_max)):
-            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
-                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
+        _ra.check_named_shapes(who, (("q_ref", q_ref, su), ("qd_ref", qd_ref, su), ("K", K, su + (2 * n,)), ("k", k, su),
+                                    ("q0_ref", q0_ref, (Bn, n)), ("qd0_ref", qd0_ref, (Bn, n)), ("du", du, lead_du)))
+        _ra.check_limits(who, u_min, u_max, n)
         cd = cost.dense(T, Bn, n)                 # (raises on a shape that is none of the accepted forms)
-        (q0, qd0), _, is_np, dev, dtp = self._prep(q0, qd0)
-
-        def dev_of(x):
-            if x is None:
-                return None
-            if isinstance(x, torch.Tensor):
-                if is_np:
-                    raise TypeError("mixing numpy and torch inputs is not supported")
-                if x.device != dev or x.dtype != dtp:
-                    raise TypeError("all inputs must share device and dtype")
-                return x.contiguous()
-            if not is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=dev)
-
-        u, q_ref, qd_ref, K, k, du = (dev_of(x) for x in (u, q_ref, qd_ref, K, k, du))
-        cd = {name: dev_of(x) for name, x in cd.items()}
+        (q0, qd0), cx = _ra.Ctx.from_prep(self._prep(q0, qd0))
+        u, q_ref, qd_ref, K, k, du = (cx.tensor(x) for x in (u, q_ref, qd_ref, K, k, du))
+        cd = {name: cx.tensor(x) for name, x in cd.items()}
         if K is not None:
-            q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (dev_of(q0_ref), dev_of(qd0_ref))
+            q0_ref, qd0_ref = (q0, qd0) if q0_ref is None else (cx.tensor(q0_ref), cx.tensor(qd0_ref))
         store = "trajectory" if return_trajectory else "final" if return_final else None
+        dev, dtp = cx.dev, cx.dtp
         with torch.cuda.device(dev):
-            lims = [None, None]
-            if u_min is not None:
-                for i, x in enumerate((u_min, u_max)):
-                    x = x.to(device=dev, dtype=dtp) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
-                    lims[i] = x.expand(n).contiguous()
-            rows = B * (A or 1)
-            if A is not None:
-                q0, qd0 = q0.repeat(A, 1), qd0.repeat(A, 1)          # row a B + b starts where row b does
-            al = None
-            if row_alpha is not None:
-                al = dev_of(row_alpha)
-            elif k is not None:
-                if A is None:
-                    al = torch.full((rows,), float(alpha), device=dev, dtype=dtp)
-                else:
-                    a1 = alpha.to(device=dev, dtype=dtp) if isinstance(alpha, torch.Tensor) else torch.as_tensor(np.asarray(alpha, dtype=np.float64), device=dev).to(dtp)
-                    al = a1.repeat_interleave(B).contiguous()
+            lo, hi = cx.limits(u_min, u_max, n)
+            q0, qd0, al, rows = cx.alpha_rows(q0, qd0, alpha, A, row_alpha, k, B)
             J = torch.empty((rows,), device=dev, dtype=dtp)
             q = qd = ua = None
             if store is not None:
@@ -1196,21 +1053,18 @@ class RBDReference:
                 qd = torch.empty_like(q)
             if store == "trajectory":
                 ua = torch.empty((T, rows, n), device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             self._lib.check(self._fn("rbd_rollout_cost", dtp)(
                 self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(k), self._ptr(K), self._ptr(q0_ref), self._ptr(qd0_ref),
-                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(du), self._ptr(lims[0]), self._ptr(lims[1]),
+                self._ptr(q_ref), self._ptr(qd_ref), self._ptr(al), self._ptr(du), self._ptr(lo), self._ptr(hi),
                 self._ptr(cd["q_target"]), self._ptr(cd["qd_target"]), self._ptr(cd["w_q"]), self._ptr(cd["w_qd"]),
                 int(cost.terminal_state_only), self._ptr(cd["w_u"]), self._ptr(cd["c_u"]), float(dt), float(GRAVITY),
                 RBD_INTEGRATORS[integrator], rows, Bn, T, self._ptr(J), self._ptr(q), self._ptr(qd),
-                int(store == "trajectory"), self._ptr(ua), st))
+                int(store == "trajectory"), self._ptr(ua), cx.stream()))
         outs = [J if A is None else J.view(A, B)]
         for x in (q, qd, ua):
             if x is not None:
                 outs.append(x if A is None else x.view(*x.shape[:-2], A, B, n))
-        if is_np:
-            outs = [x.cpu().numpy() for x in outs]
-        return outs[0] if store is None else tuple(outs)
+        return cx.to_caller(outs[0] if store is None else tuple(outs))
 
     # ---- iLQR: rollout_lqr -> rollout_cost (line search) -> rollout_closed_loop (forward pass), per-row accept / reject ----
     def ilqr(self, q0, qd0, u, dt, cost, iters=10, alphas=(1, .5, .25, .125, .03125, .0078125), reg=0.0, u_min=None,
@@ -1235,17 +1089,12 @@ class RBDReference:
         such joints (see ``rollout_lqr``), so the gains are not those of the true linearisation there; the line search
         still never accepts a step that raises the cost.  Fixed-base robots only."""
         from .cost import QuadraticCost
-        who = "ilqr"
-        if self.model.floating:
-            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
+        who, n = "ilqr", self.n
+        _ra.check_base_integrator(who, self.model.floating)
         if not isinstance(cost, QuadraticCost):
             raise TypeError(f"{who}: cost must be a QuadraticCost")
-        n = self.n
-        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))
-        if len(sq) != 2 or sq[1] != n or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"{who}: q0 and qd0 must both be [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        if len(su) != 3 or su[1:] != sq or su[0] == 0:
-            raise ValueError(f"{who}: u must be [T, {sq[0]}, {n}] (time-major, T > 0), got {su}")
+        B = _ra.check_state(who, n, q0, qd0, unbatched=False)[0]
+        _ra.check_u_steps(who, n, u, B)
         iters = int(iters)
         if iters < 0:
             raise ValueError(f"{who}: iters < 0")
@@ -1254,17 +1103,8 @@ class RBDReference:
         regs = [float(reg)] * iters if np.ndim(reg) == 0 else [float(r) for r in reg]
         if len(regs) != iters:
             raise ValueError(f"{who}: reg must be a float or a sequence of iters = {iters} floats, got {len(regs)}")
-        is_np = not isinstance(q0, torch.Tensor)
-        if is_np:
-            if any(isinstance(x, torch.Tensor) for x in (qd0, u, *(getattr(cost, a) for a in _COST_ARRAYS))):
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            if not torch.cuda.is_available():
-                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
-            up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0")   # noqa: E731
-            q0, qd0, u = up(q0), up(qd0), up(u)
-            cost = QuadraticCost(*(up(getattr(cost, a)) for a in _COST_ARRAYS),
-                                 terminal_state_only=cost.terminal_state_only)
-        dev, dtp = q0.device, q0.dtype
+        cx, q0, qd0, u, _, cost = _ra.Ctx.upload(q0, qd0, u, None, cost, strict=False)
+        dev, dtp = cx.dev, cx.dtp
         kw = dict(GRAVITY=GRAVITY, integrator=integrator)
         lim = dict(u_min=u_min, u_max=u_max)
         with torch.cuda.device(dev):
@@ -1292,29 +1132,13 @@ class RBDReference:
                 h_al.append(ra)
                 h_dV.append(dV)
                 h_st.append(status)
-            B = sq[0]
             res = IlqrResult(u, q, qd, torch.stack(hist),
                              torch.stack(h_al) if iters else torch.empty((0, B), device=dev, dtype=dtp),
                              torch.stack(h_dV) if iters else torch.empty((0, B, 2), device=dev, dtype=dtp),
                              torch.stack(h_st) if iters else torch.empty((0, B), device=dev, dtype=torch.int32))
-        return IlqrResult(*(x.cpu().numpy() for x in res)) if is_np else res
+        return cx.to_caller(res)
 
     # ---- MPPI: rollout_cost (the sample costs) -> mppi_update (softmin weights, weighted sum of the perturbations) ----
-    @staticmethod
-    def _mppi_limits(who, u_min, u_max, n):
-        if (u_min is None) != (u_max is None):
-            raise ValueError(f"{who}: give u_min and u_max together, or neither")
-        for name, x in (("u_min", u_min), ("u_max", u_max)):
-            if x is not None and tuple(np.shape(x)) not in ((), (n,)):
-                raise ValueError(f"{who}: {name} must be a scalar or [{n}], got {tuple(np.shape(x))}")
-
-    @staticmethod
-    def _mppi_small(x, dev, dtp):
-        """A float, sequence, array or tensor as a tensor of the call's device and dtype (lam, sigma, the limits)."""
-        if isinstance(x, torch.Tensor):
-            return x.to(device=dev, dtype=dtp)
-        return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).to(dtp)
-
     def mppi_update(self, J, du, u, lam, u_min=None, u_max=None, return_weights=False):
         """The update of a sampling controller from the sample costs ``rollout_cost`` wrote -> ``MppiUpdate(u, w, ess,
         status)``.  Not part of the reference.  ``P`` independent problems with ``S`` samples each, in ``rollout_cost``'s
@@ -1332,57 +1156,34 @@ class RBDReference:
         on ``P``, ``T`` or ``return_weights``.  ``w [S, P]`` is ``None`` unless ``return_weights``.
         numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
         Fixed-base robots only."""
-        who = "mppi_update"
-        if self.model.floating:
-            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
-        n = self.n
-        sJ, sd, su = tuple(np.shape(J)), tuple(np.shape(du)), tuple(np.shape(u))
+        who, n = "mppi_update", self.n
+        _ra.check_base_integrator(who, self.model.floating)
+        sJ = tuple(np.shape(J))
         if len(sJ) != 2 or 0 in sJ:
             raise ValueError(f"{who}: J must be [S, P] with S, P > 0, got {sJ}")
         S, P = sJ
-        if len(su) != 3 or su[1:] != (P, n) or su[0] == 0:
-            raise ValueError(f"{who}: u must be [T, {P}, {n}] (time-major, T > 0), got {su}")
-        T = su[0]
-        if sd != (T, S, P, n):
-            raise ValueError(f"{who}: du must be {[T, S, P, n]}, got {sd}")
+        T = _ra.check_u_steps(who, n, u, P)
+        _ra.check_named_shapes(who, (("du", du, (T, S, P, n)),))
         if tuple(np.shape(lam)) not in ((), (P,)):
             raise ValueError(f"{who}: lam must be a float or [{P}], got shape {tuple(np.shape(lam))}")
-        self._mppi_limits(who, u_min, u_max, n)
-        is_np = not isinstance(J, torch.Tensor)
-        if any(isinstance(x, torch.Tensor) == is_np for x in (du, u)):
-            raise TypeError("mixing numpy and torch inputs is not supported")
-        if is_np:
-            if not torch.cuda.is_available():
-                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
-            J, du, u = (torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0") for x in (J, du, u))
-        dev, dtp = J.device, J.dtype
-        if dev.type != "cuda":
-            raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
-        if dtp not in (_F32, _F64):
-            raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
-        if any(x.device != dev or x.dtype != dtp for x in (du, u)):
-            raise TypeError("all inputs must share device and dtype")
-        esz = 4 if dtp == _F32 else 8
-        sfx = "f32" if esz == 4 else "f64"
+        _ra.check_limits(who, u_min, u_max, n)
+        cx = _ra.Ctx.from_first(J, du, u)
+        J, du, u = (cx.tensor(x) for x in (J, du, u))
+        dev, dtp, esz, sfx = cx.dev, cx.dtp, cx.esz, cx.sfx
         with torch.cuda.device(dev):
-            J, du, u = J.contiguous(), du.contiguous(), u.contiguous()
-            lam_t = self._mppi_small(lam, dev, dtp).expand(P).contiguous()
-            lo = hi = None
-            if u_min is not None:
-                lo, hi = (self._mppi_small(x, dev, dtp).expand(n).contiguous() for x in (u_min, u_max))
+            lam_t = cx.small(lam).expand(P).contiguous()
+            lo, hi = cx.limits(u_min, u_max, n)
             u_new = torch.empty((T, P, n), device=dev, dtype=dtp)
             w = torch.empty((S, P), device=dev, dtype=dtp) if return_weights else None
             ess = torch.empty((P,), device=dev, dtype=dtp)
             status = torch.empty((P,), device=dev, dtype=torch.int32)
-            st = torch.cuda.current_stream(dev).cuda_stream
             lib = self._lib.resolve("rbd_mppi_update", sfx)     # ONE resolution: workspace size and entry point from the same library
             wsb = int(lib.rbd_mppi_update_workspace_bytes(S, P, T, esz))
             ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
             self._lib.check(getattr(lib, f"rbd_mppi_update_{sfx}")(
                 self._ptr(J), self._ptr(du), self._ptr(u), self._ptr(lam_t), self._ptr(lo), self._ptr(hi), S, P, T, self._ptr(u_new),
-                self._ptr(w), self._ptr(ess), self._ptr(status), ws.data_ptr(), wsb, st))
-        res = MppiUpdate(u_new, w, ess, status)
-        return MppiUpdate(*(None if x is None else x.cpu().numpy() for x in res)) if is_np else res
+                self._ptr(w), self._ptr(ess), self._ptr(status), ws.data_ptr(), wsb, cx.stream()))
+        return cx.to_caller(MppiUpdate(u_new, w, ess, status))
 
     def mppi(self, q0, qd0, u, dt, cost, iters=1, samples=1024, sigma=0.1, lam=1.0, noise=None, generator=None, u_min=None,
              u_max=None, GRAVITY=-9.81, integrator="semi_implicit"):
@@ -1404,22 +1205,16 @@ class RBDReference:
         problem, which the softmin does not see.  Not included: shifting the nominal between the steps of a receding
         horizon, and feedback gains around the samples.
         numpy in -> float64 numpy out; tensors stay on their device and dtype.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
         from .cost import QuadraticCost
-        who = "mppi"
-        if self.model.floating:
-            raise NotImplementedError(f"{who}: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"{who}: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
+        who, n = "mppi", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
         if not isinstance(cost, QuadraticCost):
             raise TypeError(f"{who}: cost must be a QuadraticCost")
-        n = self.n
-        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))
+        sq = tuple(np.shape(q0))                  # (inline: P > 0 is part of this method's rule and message)
         if len(sq) != 2 or sq[1] != n or sq[0] == 0 or tuple(np.shape(qd0)) != sq:
             raise ValueError(f"{who}: q0 and qd0 must both be [P, {n}] with P > 0, got {sq} and {tuple(np.shape(qd0))}")
-        if len(su) != 3 or su[1:] != sq or su[0] == 0:
-            raise ValueError(f"{who}: u must be [T, {sq[0]}, {n}] (time-major, T > 0), got {su}")
-        T, P = su[0], sq[0]
+        P = sq[0]
+        T = _ra.check_u_steps(who, n, u, P)
         iters = int(iters)
         if iters < 0:
             raise ValueError(f"{who}: iters < 0")
@@ -1438,30 +1233,17 @@ class RBDReference:
             raise ValueError(f"{who}: sigma must be a float, [{n}] or [{T}, {n}], got shape {tuple(np.shape(sigma))}")
         if tuple(np.shape(lam)) not in ((), (P,)):
             raise ValueError(f"{who}: lam must be a float or [{P}], got shape {tuple(np.shape(lam))}")
-        self._mppi_limits(who, u_min, u_max, n)
-        is_np = not isinstance(q0, torch.Tensor)
-        others = (qd0, u, *(getattr(cost, a) for a in _COST_ARRAYS)) + (() if noise is None else (noise,))
-        if is_np:
-            if any(isinstance(x, torch.Tensor) for x in others):
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            if not torch.cuda.is_available():
-                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
-            up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device="cuda:0")   # noqa: E731
-            q0, qd0, u, noise = up(q0), up(qd0), up(u), up(noise)
-            cost = QuadraticCost(*(up(getattr(cost, a)) for a in _COST_ARRAYS),
-                                 terminal_state_only=cost.terminal_state_only)
-        elif not all(isinstance(x, torch.Tensor) for x in (qd0, u) + (() if noise is None else (noise,))):
-            raise TypeError("mixing numpy and torch inputs is not supported")
-        dev, dtp = q0.device, q0.dtype
+        _ra.check_limits(who, u_min, u_max, n)
+        cx, q0, qd0, u, noise, cost = _ra.Ctx.upload(q0, qd0, u, noise, cost, strict=True)
+        dev, dtp = cx.dev, cx.dtp
         kw = dict(GRAVITY=GRAVITY, integrator=integrator)
         with torch.cuda.device(dev):
-            lim = dict(u_min=None, u_max=None)                         # the small tensors are made once, before the loop
-            if u_min is not None:
-                lim = dict(u_min=self._mppi_small(u_min, dev, dtp).expand(n).contiguous(), u_max=self._mppi_small(u_max, dev, dtp).expand(n).contiguous())
-            sg = self._mppi_small(sigma, dev, dtp)
+            lo, hi = cx.limits(u_min, u_max, n)                        # the small tensors are made once, before the loop
+            lim = dict(u_min=lo, u_max=hi)
+            sg = cx.small(sigma)
             if sg.dim() == 2:
                 sg = sg[:, None, None, :]
-            lam_t = self._mppi_small(lam, dev, dtp).expand(P).contiguous()
+            lam_t = cx.small(lam).expand(P).contiguous()
             q0s, qd0s = q0.repeat(S, 1), qd0.repeat(S, 1)              # row s P + p starts where problem p does
             hist, h_ess, h_st = [], [], []
             for it in range(iters):
@@ -1479,22 +1261,9 @@ class RBDReference:
             res = MppiResult(u, q, qd, torch.stack(hist),
                              torch.stack(h_ess) if iters else torch.empty((0, P), device=dev, dtype=dtp),
                              torch.stack(h_st) if iters else torch.empty((0, P), device=dev, dtype=torch.int32))
-        return MppiResult(*(x.cpu().numpy() for x in res)) if is_np else res
+        return cx.to_caller(res)
 
     # ---- reverse-mode gradient of a rollout: rbd_rollout_grad (aba, rnea_grad, minv per chunk + one scan launch) ------
-    _ROLLG_WS_CAP = 1 << 30
-
-    @staticmethod
-    def _rollg_g_shape(gq, gqd, T, B, n, unb, who):
-        """Shape check of the two cost gradients, before anything touches the GPU -> g_final_only."""
-        if gq is None and gqd is None:
-            raise ValueError(f"{who}: give grad_q, grad_qd or both (the gradient of the cost with respect to the trajectory)")
-        full, fin = ((T, n), (n,)) if unb else ((T, B, n), (B, n))
-        shapes = [tuple(np.shape(g)) for g in (gq, gqd) if g is not None]
-        if any(sh not in (full, fin) for sh in shapes) or len(set(shapes)) != 1:
-            raise ValueError(f"{who}: grad_q and grad_qd must both be {list(full)} or both {list(fin)} (final state), got {shapes}")
-        return shapes[0] == fin
-
     def rollout_grad(self, q0, qd0, u, dt, grad_q=None, grad_qd=None, GRAVITY=-9.81, integrator="semi_implicit",
                      q=None, qd=None, workspace_bytes=None):
         """Reverse-mode gradient of ``rollout``: for a scalar cost ``L`` of the returned slices, with
@@ -1516,52 +1285,15 @@ class RBDReference:
         Robots with PRISMATIC joints: ``rnea_grad``'s ``dc_dq`` reproduces the reference and is not the q-derivative for
         such joints (see ``fdsva_so``), and this gradient inherits that: it is the true gradient on robots with
         revolute joints only.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
-        if self.model.floating:
-            raise NotImplementedError("rollout_grad: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"rollout_grad: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
-        n = self.n
-        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
-        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"rollout_grad: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        unb = len(sq) == 1
-        B = 1 if unb else sq[0]
-        shared = len(su) == 2
-        if unb and not shared:
-            raise ValueError(f"rollout_grad: q0 [{n}] takes u [T, {n}], got {su}")
-        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
-            raise ValueError(f"rollout_grad: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
-        T = su[0]
-        if T == 0:
-            raise ValueError("rollout_grad: u holds no step (T == 0)")
-        final = self._rollg_g_shape(grad_q, grad_qd, T, B, n, unb, "rollout_grad")
-        if (q is None) != (qd is None):
-            raise ValueError("rollout_grad: give both q and qd (the trajectory of rollout) or neither")
-        traj = (T, n) if unb else (T, B, n)
-        if q is not None and (tuple(np.shape(q)) != traj or tuple(np.shape(qd)) != traj):
-            raise ValueError(f"rollout_grad: q and qd must be the trajectory {list(traj)}, got {tuple(np.shape(q))} and {tuple(np.shape(qd))}")
-        if workspace_bytes is not None and int(workspace_bytes) < 0:
-            raise ValueError("rollout_grad: workspace_bytes < 0")
-        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
-
-        def dev_tensor(x):
-            if isinstance(x, torch.Tensor):
-                if is_np:
-                    raise TypeError("mixing numpy and torch inputs is not supported")
-                if x.device != dev or x.dtype != dtp:
-                    raise TypeError("all inputs must share device and dtype")
-                return x.contiguous()
-            if not is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).contiguous()
-        u = dev_tensor(u)
-        gq = None if grad_q is None else dev_tensor(grad_q)
-        gqd = None if grad_qd is None else dev_tensor(grad_qd)
-        if q is not None:
-            q, qd = dev_tensor(q), dev_tensor(qd)
-        esz = 4 if dtp == torch.float32 else 8
-        sfx = "f32" if esz == 4 else "f64"
+        who, n = "rollout_grad", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
+        unb, B, T, shared = _ra.check_shapes(who, n, q0, qd0, u)
+        final = _ra.rollg_g_shape(grad_q, grad_qd, T, B, n, unb, who)
+        _ra.check_trajectory(who, q, qd, T, B, n, unb)
+        _ra.check_workspace_request(who, workspace_bytes)
+        (q0, qd0), cx = _ra.Ctx.from_prep(self._prep(q0, qd0))
+        u, gq, gqd, q, qd = (cx.tensor(x) for x in (u, grad_q, grad_qd, q, qd))
+        dev, dtp, esz, sfx = cx.dev, cx.dtp, cx.esz, cx.sfx
         with torch.cuda.device(dev):
             if shared:
                 u = u[:, None, :].expand(T, B, n).contiguous()
@@ -1570,23 +1302,18 @@ class RBDReference:
             gu = torch.empty((T, B, n), device=dev, dtype=dtp)
             gq0 = torch.empty((B, n), device=dev, dtype=dtp)
             gqd0 = torch.empty((B, n), device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             lib = self._lib.resolve("rbd_rollout_grad", sfx)    # ONE resolution: workspace size and entry point from the same library
-            if workspace_bytes is None:
-                wsb = int(lib.rbd_rollout_grad_workspace_bytes(B, T, esz))
-                wsb = max(min(wsb, self._ROLLG_WS_CAP), int(lib.rbd_rollout_grad_workspace_bytes(B, 1, esz)))
-            else:
-                wsb = int(workspace_bytes)
+            wsb = _ra.workspace_bytes(lib.rbd_rollout_grad_workspace_bytes, B, T, esz, workspace_bytes)
             ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
             self._lib.check(getattr(lib, f"rbd_rollout_grad_{sfx}")(
                 self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(q), self._ptr(qd), self._ptr(gq), self._ptr(gqd), int(final),
                 float(dt), float(GRAVITY), RBD_INTEGRATORS[integrator], B, T, self._ptr(gu), self._ptr(gq0), self._ptr(gqd0),
-                ws.data_ptr(), wsb, st))
+                ws.data_ptr(), wsb, cx.stream()))
             if shared:
                 gu = gu.sum(1)
         if unb:
             gq0, gqd0 = gq0[0], gqd0[0]
-        return tuple(x.cpu().numpy() for x in (gu, gq0, gqd0)) if is_np else (gu, gq0, gqd0)
+        return cx.to_caller((gu, gq0, gqd0))
 
     def rollout_adjoint(self, dc_du, Minv, dt, grad_q=None, grad_qd=None, integrator="semi_implicit", lam=None):
         """The scan of ``rollout_grad`` alone (``rbd_rollout_adjoint``), for a caller who holds the linearisation:
@@ -1597,94 +1324,23 @@ class RBDReference:
         over, bit-identical to one call.  ``grad_q, grad_qd``: ``[T, B, n]``, or ``[B, n]`` for the last of these steps
         alone.  numpy in -> float64 numpy out; tensors stay on their device and dtype and run on torch's current stream.
         The prismatic-joint caveat of ``rollout_grad`` applies.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
-        if self.model.floating:
-            raise NotImplementedError("rollout_adjoint: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"rollout_adjoint: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
-        n = self.n
-        sd, sm = tuple(np.shape(dc_du)), tuple(np.shape(Minv))
-        if len(sd) != 4 or sd[2:] != (n, 2 * n) or sm != sd[:2] + (n, n):
-            raise ValueError(f"rollout_adjoint: dc_du must be [T, B, {n}, {2 * n}] and Minv [T, B, {n}, {n}], got {sd} and {sm}")
-        T, B = sd[:2]
-        if T == 0:
-            raise ValueError("rollout_adjoint: no step (T == 0)")
-        final = self._rollg_g_shape(grad_q, grad_qd, T, B, n, False, "rollout_adjoint")
-        if lam is not None and tuple(np.shape(lam)) != (B, 2 * n):
-            raise ValueError(f"rollout_adjoint: lam must be [{B}, {2 * n}], got {tuple(np.shape(lam))}")
-        is_np = not isinstance(dc_du, torch.Tensor)
-        if is_np:
-            if not torch.cuda.is_available():
-                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
-            dev, dtp = torch.device("cuda", 0), torch.float64
-        else:
-            dev, dtp = dc_du.device, dc_du.dtype
-            if dev.type != "cuda":
-                raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
-            if dtp not in (torch.float32, torch.float64):
-                raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
-
-        def dev_tensor(x):
-            if x is None:
-                return None
-            if isinstance(x, torch.Tensor):
-                if is_np:
-                    raise TypeError("mixing numpy and torch inputs is not supported")
-                if x.device != dev or x.dtype != dtp:
-                    raise TypeError("all inputs must share device and dtype")
-                return x.contiguous()
-            if not is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            return torch.as_tensor(np.asarray(x, dtype=np.float64), device=dev).contiguous()
-        dc_du, Minv, gq, gqd = (dev_tensor(x) for x in (dc_du, Minv, grad_q, grad_qd))
+        who, n = "rollout_adjoint", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
+        T, B = _ra.check_linearisation(who, dc_du, Minv, n)
+        final = _ra.rollg_g_shape(grad_q, grad_qd, T, B, n, False, who)
+        _ra.check_named_shapes(who, (("lam", lam, (B, 2 * n)),))
+        cx = _ra.Ctx.from_first(dc_du)
+        dc_du, Minv, gq, gqd = (cx.tensor(x) for x in (dc_du, Minv, grad_q, grad_qd))
+        dev, dtp = cx.dev, cx.dtp
         with torch.cuda.device(dev):
-            if lam is None:
-                lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp)
-            else:
-                lam_t = dev_tensor(lam)
+            lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp) if lam is None else cx.tensor(lam)
             gu = torch.empty((T, B, n), device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             self._lib.check(self._fn("rbd_rollout_adjoint", dtp)(
                 self._ptr(dc_du), self._ptr(Minv), self._ptr(gq), self._ptr(gqd), int(final), float(dt),
-                RBD_INTEGRATORS[integrator], B, T, self._ptr(lam_t), self._ptr(gu), st))
-        return (gu.cpu().numpy(), lam_t.cpu().numpy()) if is_np else (gu, lam_t)
+                RBD_INTEGRATORS[integrator], B, T, self._ptr(lam_t), self._ptr(gu), cx.stream()))
+        return cx.to_caller((gu, lam_t))
 
     # ---- backward pass of iLQR / DDP over a rollout: rbd_rollout_lqr (aba, rnea_grad, minv per chunk + the Riccati scan) ----
-    @staticmethod
-    def _lqr_cost_shapes(T, B, n, unb, who, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg):
-        """Shape and value checks of the cost model, before anything touches the GPU -> (x_final_only, hu_shared)."""
-        if hess_u is None:
-            raise ValueError(f"{who}: hess_u is required (the diagonal of the control cost's Hessian, [T, B, n] or [n])")
-        full, fin = ((T, n), (n,)) if unb else ((T, B, n), (B, n))
-        shapes = [tuple(np.shape(a)) for a in (grad_q, grad_qd, hess_q, hess_qd) if a is not None]
-        if any(sh not in (full, fin) for sh in shapes) or len(set(shapes)) > 1:
-            raise ValueError(f"{who}: grad_q, grad_qd, hess_q and hess_qd must all be {list(full)} or all {list(fin)} "
-                             f"(last step only), got {shapes}")
-        if grad_u is not None and tuple(np.shape(grad_u)) != full:
-            raise ValueError(f"{who}: grad_u must be {list(full)}, got {tuple(np.shape(grad_u))}")
-        sh = tuple(np.shape(hess_u))
-        if sh != (n,) and sh != full:          # (unbatched: [T, n] is per step, [n] is shared)
-            raise ValueError(f"{who}: hess_u must be {list(full)} or [{n}] (shared by every row and step), got {sh}")
-        if not (np.isfinite(reg) and reg >= 0):
-            raise ValueError(f"{who}: reg must be finite and >= 0, got {reg}")
-        return bool(shapes) and shapes[0] == fin, sh == (n,)
-
-    @staticmethod
-    def _lqr_dev_tensor(x, is_np, dev, dtp):
-        """An optional input of rollout_lqr / rollout_riccati as a contiguous device tensor of dtype ``dtp`` (int32 for
-        ``status``); numpy and torch inputs do not mix."""
-        if x is None:
-            return None
-        if isinstance(x, torch.Tensor):
-            if is_np:
-                raise TypeError("mixing numpy and torch inputs is not supported")
-            if x.device != dev or x.dtype != dtp:
-                raise TypeError("all inputs must share device and dtype (status: int32)")
-            return x.contiguous()
-        if not is_np:
-            raise TypeError("mixing numpy and torch inputs is not supported")
-        return torch.as_tensor(np.asarray(x, dtype=np.int32 if dtp == torch.int32 else np.float64), device=dev).contiguous()
-
     def rollout_lqr(self, q0, qd0, u, dt, grad_q=None, grad_qd=None, hess_q=None, hess_qd=None, grad_u=None, hess_u=None,
                     reg=0.0, GRAVITY=-9.81, integrator="semi_implicit", q=None, qd=None, workspace_bytes=None):
         """Backward pass of iLQR / DDP / time-varying LQR along a rollout: from the linearisation of every step and a
@@ -1710,39 +1366,15 @@ class RBDReference:
         Robots with PRISMATIC joints: ``rnea_grad``'s ``dc_dq`` reproduces the reference and is not the q-derivative for
         such joints (see ``rollout_grad``), and the gains inherit that: they belong to the true linearisation on robots
         with revolute joints only.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
-        if self.model.floating:
-            raise NotImplementedError("rollout_lqr: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"rollout_lqr: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
-        n = self.n
-        sq, su = tuple(np.shape(q0)), tuple(np.shape(u))      # shapes first: refused before anything touches the GPU
-        if sq not in ((n,), sq[:1] + (n,)) or tuple(np.shape(qd0)) != sq:
-            raise ValueError(f"rollout_lqr: q0 and qd0 must both be [{n}] or [B, {n}], got {sq} and {tuple(np.shape(qd0))}")
-        unb = len(sq) == 1
-        B = 1 if unb else sq[0]
-        shared = len(su) == 2
-        if unb and not shared:
-            raise ValueError(f"rollout_lqr: q0 [{n}] takes u [T, {n}], got {su}")
-        if len(su) not in (2, 3) or su[1:] != ((n,) if shared else (B, n)):
-            raise ValueError(f"rollout_lqr: u must be [T, {B}, {n}] or [T, {n}] (time-major), got {su}")
-        T = su[0]
-        if T == 0:
-            raise ValueError("rollout_lqr: u holds no step (T == 0)")
-        final, hu_shared = self._lqr_cost_shapes(T, B, n, unb, "rollout_lqr", grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg)
-        if (q is None) != (qd is None):
-            raise ValueError("rollout_lqr: give both q and qd (the trajectory of rollout) or neither")
-        traj = (T, n) if unb else (T, B, n)
-        if q is not None and (tuple(np.shape(q)) != traj or tuple(np.shape(qd)) != traj):
-            raise ValueError(f"rollout_lqr: q and qd must be the trajectory {list(traj)}, got {tuple(np.shape(q))} and {tuple(np.shape(qd))}")
-        if workspace_bytes is not None and int(workspace_bytes) < 0:
-            raise ValueError("rollout_lqr: workspace_bytes < 0")
-        (q0, qd0), unb, is_np, dev, dtp = self._prep(q0, qd0)
-
-        dev_tensor = lambda x: self._lqr_dev_tensor(x, is_np, dev, dtp)      # noqa: E731
-        u, gq, gqd, hq, hqd, gu, hu, q, qd = (dev_tensor(x) for x in (u, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, q, qd))
-        esz = 4 if dtp == torch.float32 else 8
-        sfx = "f32" if esz == 4 else "f64"
+        who, n = "rollout_lqr", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
+        unb, B, T, shared = _ra.check_shapes(who, n, q0, qd0, u)
+        final, hu_shared = _ra.lqr_cost_shapes(T, B, n, unb, who, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg)
+        _ra.check_trajectory(who, q, qd, T, B, n, unb)
+        _ra.check_workspace_request(who, workspace_bytes)
+        (q0, qd0), cx = _ra.Ctx.from_prep(self._prep(q0, qd0))
+        u, gq, gqd, hq, hqd, gu, hu, q, qd = (cx.tensor(x) for x in (u, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, q, qd))
+        dev, dtp, esz, sfx = cx.dev, cx.dtp, cx.esz, cx.sfx
         with torch.cuda.device(dev):
             if shared:
                 u = u[:, None, :].expand(T, B, n).contiguous()
@@ -1754,23 +1386,18 @@ class RBDReference:
             P = torch.empty((B, 2 * n, 2 * n), device=dev, dtype=dtp)
             dV = torch.empty((B, 2), device=dev, dtype=dtp)
             status = torch.empty((B,), device=dev, dtype=torch.int32)
-            st = torch.cuda.current_stream(dev).cuda_stream
             lib = self._lib.resolve("rbd_rollout_lqr", sfx)     # ONE resolution: workspace size and entry point from the same library
-            if workspace_bytes is None:
-                wsb = int(lib.rbd_rollout_lqr_workspace_bytes(B, T, esz))
-                wsb = max(min(wsb, self._ROLLG_WS_CAP), int(lib.rbd_rollout_lqr_workspace_bytes(B, 1, esz)))
-            else:
-                wsb = int(workspace_bytes)
+            wsb = _ra.workspace_bytes(lib.rbd_rollout_lqr_workspace_bytes, B, T, esz, workspace_bytes)
             ws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
             self._lib.check(getattr(lib, f"rbd_rollout_lqr_{sfx}")(
                 self._ptr(q0), self._ptr(qd0), self._ptr(u), self._ptr(q), self._ptr(qd), self._ptr(gq), self._ptr(gqd),
                 self._ptr(hq), self._ptr(hqd), int(final), self._ptr(gu), self._ptr(hu), int(hu_shared), float(reg), float(dt),
                 float(GRAVITY), RBD_INTEGRATORS[integrator], B, T, self._ptr(k), self._ptr(K), self._ptr(lam), self._ptr(P),
-                self._ptr(dV), self._ptr(status), ws.data_ptr(), wsb, st))
+                self._ptr(dV), self._ptr(status), ws.data_ptr(), wsb, cx.stream()))
         out = (k, K, lam, P, dV, status)
         if unb:
             out = (k[:, 0], K[:, 0], lam[0], P[0], dV[0], status[0])
-        return tuple(x.cpu().numpy() for x in out) if is_np else out
+        return cx.to_caller(out)
 
     def rollout_riccati(self, dc_du, Minv, dt, grad_q=None, grad_qd=None, hess_q=None, hess_qd=None, grad_u=None, hess_u=None,
                         reg=0.0, integrator="semi_implicit", lam=None, P=None, dV=None, status=None):
@@ -1785,51 +1412,26 @@ class RBDReference:
         costs belongs to the last of THESE steps.  numpy in -> float64 numpy out; tensors stay on their device and dtype
         and run on torch's current stream.  The prismatic-joint caveat of ``rollout_grad`` applies to a linearisation
         that comes from ``rnea_grad``.  Fixed-base robots only."""
-        from ._lib import RBD_INTEGRATORS
-        if self.model.floating:
-            raise NotImplementedError("rollout_riccati: fixed-base robots only (rollout has no floating base)")
-        if integrator not in RBD_INTEGRATORS:
-            raise ValueError(f"rollout_riccati: unknown integrator {integrator!r}; use one of {sorted(RBD_INTEGRATORS)}")
-        n = self.n
-        sd, sm = tuple(np.shape(dc_du)), tuple(np.shape(Minv))
-        if len(sd) != 4 or sd[2:] != (n, 2 * n) or sm != sd[:2] + (n, n):
-            raise ValueError(f"rollout_riccati: dc_du must be [T, B, {n}, {2 * n}] and Minv [T, B, {n}, {n}], got {sd} and {sm}")
-        T, B = sd[:2]
-        if T == 0:
-            raise ValueError("rollout_riccati: no step (T == 0)")
-        final, hu_shared = self._lqr_cost_shapes(T, B, n, False, "rollout_riccati", grad_q, grad_qd, hess_q, hess_qd, grad_u,
-                                                 hess_u, reg)
-        for name, x, sh in (("lam", lam, (B, 2 * n)), ("P", P, (B, 2 * n, 2 * n)), ("dV", dV, (B, 2)), ("status", status, (B,))):
-            if x is not None and tuple(np.shape(x)) != sh:
-                raise ValueError(f"rollout_riccati: {name} must be {list(sh)}, got {tuple(np.shape(x))}")
-        is_np = not isinstance(dc_du, torch.Tensor)
-        if is_np:
-            if not torch.cuda.is_available():
-                raise RuntimeError("rbdreference_amd needs a ROCm GPU: numpy inputs are uploaded to cuda:0 (no CPU fallback)")
-            dev, dtp = torch.device("cuda", 0), torch.float64
-        else:
-            dev, dtp = dc_du.device, dc_du.dtype
-            if dev.type != "cuda":
-                raise RuntimeError("inputs must live on a ROCm GPU (cuda device); no CPU fallback")
-            if dtp not in (torch.float32, torch.float64):
-                raise TypeError(f"unsupported dtype {dtp}; use float32 or float64")
-
-        dev_tensor = lambda x, dt_=dtp: self._lqr_dev_tensor(x, is_np, dev, dt_)      # noqa: E731
-        dc_du, Minv, gq, gqd, hq, hqd, gu, hu = (dev_tensor(x) for x in (dc_du, Minv, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u))
+        who, n = "rollout_riccati", self.n
+        _ra.check_base_integrator(who, self.model.floating, integrator)
+        T, B = _ra.check_linearisation(who, dc_du, Minv, n)
+        final, hu_shared = _ra.lqr_cost_shapes(T, B, n, False, who, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u, reg)
+        _ra.check_named_shapes(who, (("lam", lam, (B, 2 * n)), ("P", P, (B, 2 * n, 2 * n)), ("dV", dV, (B, 2)), ("status", status, (B,))))
+        cx = _ra.Ctx.from_first(dc_du)
+        dc_du, Minv, gq, gqd, hq, hqd, gu, hu = (cx.tensor(x) for x in (dc_du, Minv, grad_q, grad_qd, hess_q, hess_qd, grad_u, hess_u))
+        dev, dtp = cx.dev, cx.dtp
         with torch.cuda.device(dev):
-            lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp) if lam is None else dev_tensor(lam)
-            P_t = torch.zeros((B, 2 * n, 2 * n), device=dev, dtype=dtp) if P is None else dev_tensor(P)
-            dV_t = torch.zeros((B, 2), device=dev, dtype=dtp) if dV is None else dev_tensor(dV)
-            st_t = torch.zeros((B,), device=dev, dtype=torch.int32) if status is None else dev_tensor(status, torch.int32)
+            lam_t = torch.zeros((B, 2 * n), device=dev, dtype=dtp) if lam is None else cx.tensor(lam)
+            P_t = torch.zeros((B, 2 * n, 2 * n), device=dev, dtype=dtp) if P is None else cx.tensor(P)
+            dV_t = torch.zeros((B, 2), device=dev, dtype=dtp) if dV is None else cx.tensor(dV)
+            st_t = torch.zeros((B,), device=dev, dtype=torch.int32) if status is None else cx.tensor(status, torch.int32)
             k = torch.empty((T, B, n), device=dev, dtype=dtp)
             K = torch.empty((T, B, n, 2 * n), device=dev, dtype=dtp)
-            st = torch.cuda.current_stream(dev).cuda_stream
             self._lib.check(self._fn("rbd_rollout_riccati", dtp)(
                 self._ptr(dc_du), self._ptr(Minv), self._ptr(gq), self._ptr(gqd), self._ptr(hq), self._ptr(hqd), int(final),
                 self._ptr(gu), self._ptr(hu), int(hu_shared), float(reg), float(dt), RBD_INTEGRATORS[integrator], B, T,
-                self._ptr(lam_t), self._ptr(P_t), self._ptr(dV_t), self._ptr(st_t), self._ptr(k), self._ptr(K), st))
-        out = (k, K, lam_t, P_t, dV_t, st_t)
-        return tuple(x.cpu().numpy() for x in out) if is_np else out
+                self._ptr(lam_t), self._ptr(P_t), self._ptr(dV_t), self._ptr(st_t), self._ptr(k), self._ptr(K), cx.stream()))
+        return cx.to_caller((k, K, lam_t, P_t, dV_t, st_t))
 
     # ---- end-effector kinematics (RBDReference.py:190-386): rbd_ee_pose, one launch per <= 16 sites -----------------
     def _ee_plan(self, ee_joint_names, ee_offsets):
